@@ -20,6 +20,11 @@ launcher's MASTER_PORT (raptor_amd.SocketComm: RCCL id, setup exchange, barriers
 ranks).  value = V-cycles/s x (global rows / 256^3): 256^3-equivalent
 V-cycles per second, the whole-job aggregate (equals plain iterations/s at N=1).
 
+A plain run (--gpus N --steps K --warmup W) sets up, warms up (PREWARM_CYCLES untimed cycles to
+reach the GPU's steady state, then the W warmup cycles), times the K steps, writes the
+solve's outputs when --dump-outputs DIR is given (dump_outputs below) and prints the headline
+result line.  Everything below is measured with --full only and added to that line:
+
 roofline: the level-0 ParCSRMatrix::mult on the plain CSR format (csr_plain_kernel: int32 row_ptr
 / col, fp64 val) timed live with HIP events on the context stream, scored on SURVEY.md 8(d)'s
 algorithmic bytes 12 nnz + 4 (n+1) + 16 n.  roofline_stored: the same mult in the product's
@@ -47,6 +52,10 @@ GRIDS = {1: (256, 256, 256), 2: (256, 256, 512), 4: (256, 512, 512), 8: (512, 51
 BOXES = {1: (1, 1, 1), 2: (1, 1, 2), 4: (1, 2, 2), 8: (2, 2, 2)}
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MALL_BYTES = 256 << 20  # Infinity Cache (MALL) capacity
+PREWARM_CYCLES = 200  # untimed cycles of a plain run before --warmup (about 0.2 s at N = 1)
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: all files of all ranks together stay below this
+DUMP_SAMPLE = 1 << 21  # entries of x kept (all ranks together) when x itself exceeds the cap
+DUMP_SEED = 42
 
 
 def log(rank, *a):
@@ -64,9 +73,18 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, everything else the benchmark measures: level "
+                         "kernels and roofline legs, cycle timeline, graph vs eager cycles, time to "
+                         "tolerance, CPU baseline (a plain run sets up, warms up, times --steps "
+                         "cycles and prints the result line)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the timed solve returned after its last step as DIR/<name>.npy "
+                         "(float64): the residual history and the iterate x (a fixed seeded sample "
+                         "of it, with the sampled indices, when x is larger than the size cap)")
     ap.add_argument("--quick", action="store_true",
-                    help="the timed solve only (no mode comparison, time to tolerance, kernel "
-                         "table or CPU baseline): rehearsals and attribution runs")
+                    help="the timed solve only, with the short rehearsal line (overrides --full): "
+                         "rehearsals and attribution runs")
     ap.add_argument("--interp", choices=["classical", "ext+i"], default="classical",
                     help="7pt: interpolation of the PMIS hierarchy (ext+i: distance two, P_max 4, one "
                          "rank; DESIGN.md 3) -- the default stays classical (time to 1e-8, DESIGN.md 6)")
@@ -89,6 +107,9 @@ def main():
                     help="PMC-measured per-launch HBM traffic of the level-0 SpMV "
                          "(scripts/gpu_profile.sh); reported as roofline.traffic")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    full = args.full and not args.quick
 
     # the bench line is the only thing on stdout: native libraries (RCCL's version banner at
     # communicator init) write to fd 1 directly, so fd 1 is pointed at stderr for the run and
@@ -194,7 +215,7 @@ def main():
     # timed solve so the timed cycles see a GPU in its steady working state: the first solve
     # after an idle setup ran ~3 % slower than the same solve repeated later in the process
     # (profiles/r5/r5d_bench_7pt.json: 1.254 vs 1.212-1.213 ms per cycle).
-    if not args.quick:
+    if full:
         # ---- level kernels, timed live with HIP events on the context stream -----------------
         n = A.local_rows
 
@@ -361,6 +382,12 @@ def main():
         del fl_src, fl_dst, rd_part
         barrier()
 
+    if not full and not args.quick:
+        # a plain run has no measurement legs in front of the timed solve, so it brings the GPU
+        # to the same steady working state with untimed cycles of the solve itself (a fixed
+        # count, the same on every rank): without them 20 timed cycles right after setup took
+        # 1.141-1.146 ms each against 1.116 behind the legs and 1.108 in the steady state
+        ml.solve(x, b, max_iter=PREWARM_CYCLES)
     # warmup (captures the cycle and norm hipGraphs, on every rank)
     if args.warmup > 0:
         ml.solve(x, b, max_iter=args.warmup)
@@ -416,6 +443,9 @@ def main():
     # the residual faster): the factor over the last 5 cycles is the asymptotic one
     conv_last5 = (float((hist[-1] / hist[-6]) ** 0.2) if len(hist) >= 6 and hist[-6] > 0 else None)
     log(rank, f"{args.steps} V-cycles in {dt * 1e3:.2f} ms -> {iters_per_s:.1f} it/s, conv {conv}")
+    if args.dump_outputs:
+        # before any later leg overwrites x: what the timed solve handed back
+        dump_outputs(args.dump_outputs, x.numpy(), hist, rank, world)
 
     def timed_solve(fn):
         """max over ranks of the wall time of fn() (a collective solve), barrier + device sync
@@ -438,6 +468,69 @@ def main():
                               "grid": list(grid), "hipgraph_all_ranks": graph_all, "graph_available": graph_avail,
                               "mode_probe": mode_probe, "partition": part_label,
                               "setup_s": round(setup_s, 2)}), file=out_stream, flush=True)
+        del ml, A
+        if world > 1:
+            comm.close()
+        return
+
+    # the headline part of the result line: all a plain run prints (--full adds its legs below)
+    head = {
+        "metric": "V-cycle iters/sec + SpMV HBM GB/s, 3D 7-pt Poisson 256^3, 1/2/4/8 MI355X",
+        "value": round(value, 3),
+        "unit": ("V-cycles/s (fixed 1.5M-row graph)" if g3 else
+                 "V-cycles/s (256^3-equivalent: rows*cycles/s / 256^3)"),
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt * 1e3 / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "strong" if g3 else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": ("synthetic (b = A x*, x* splitmix64 U(-1,1) seed 42, x0 = 0)" +
+                 ("; matrix: seeded graph-Laplacian SUBSTITUTE for SuiteSparse G3_circuit "
+                  "(not available offline)" if g3 else "")),
+        "config": {
+            "workload": (f"G3_circuit substitute: graph Laplacian on a {grid[0]}x{grid[1]} lattice "
+                         f"({n_global} rows, {infos[0]['nnz_global']} nnz, seed 1), "
+                         f"{'random numbering' if args.no_reorder else 'RCM-reordered'}, smoothed "
+                         f"aggregation (MIS(2)), hybrid GS(64) 1+1 V-cycle, {part_label}" +
+                         (f", coarse drop tolerance {drop_tol:g}" if drop_tol else ""))
+            if g3 else
+            (f"3D 27-pt Q1 anisotropic diffusion (1,1,1e-3) {grid[0]}x{grid[1]}x{grid[2]}, "
+             f"smoothed aggregation (MIS(2)), hybrid GS(64) 1+1 V-cycle, {part_label}" +
+             (f", coarse drop tolerance {drop_tol:g}" if drop_tol else ""))
+            if sa27 else
+            (f"3D 7-pt Poisson {grid[0]}x{grid[1]}x{grid[2]}, PMIS + "
+             f"{'classical' if args.interp == 'classical' else 'extended+i (P_max 4)'} interp, "
+             f"Jacobi(2/3) 1+1 V-cycle, {part_label}" +
+             (f", coarse drop tolerance {drop_tol:g} (non-Galerkin)" if drop_tol else "")),
+            "grid": list(grid),
+            "global_rows": n_global,
+            "levels": nlev,
+            "level_rows": [i["n_global"] for i in infos],
+            "level_nnz": [i["nnz_global"] for i in infos],
+            "operator_complexity": round(sum(i["nnz_global"] for i in infos) / infos[0]["nnz_global"], 3),
+            # the densest coarse level's mean nonzeros per row
+            "coarse_nnz_per_row_max": max((round(i["nnz_global"] / max(1, i["n_global"]), 1)
+                                           for i in infos[1:]), default=None),
+            "drop_tol": drop_tol,
+            "parallelism": f"row-partition x{world}, RCCL halo",
+            "partition": part_label,
+            "setup_s": round(setup_s, 2),
+            "reorder_s": None if reorder_s is None else round(reorder_s, 2),
+            "hipgraph": graph_used,
+            "hipgraph_all_ranks": graph_all,  # the timed mode (the probe's choice at N > 1)
+            "graph_available": graph_avail,
+            "gs_split_per_rank_level": gs_split,
+        },
+        "iters_per_s": round(iters_per_s, 3),
+        "convergence_factor": conv,
+        "convergence_factor_last5": conv_last5,
+    }
+    if not full:
+        if rank == 0:
+            print(json.dumps(dict(head, runtime=ra.runtime_versions())), file=out_stream, flush=True)
         del ml, A
         if world > 1:
             comm.close()
@@ -527,58 +620,7 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": "V-cycle iters/sec + SpMV HBM GB/s, 3D 7-pt Poisson 256^3, 1/2/4/8 MI355X",
-            "value": round(value, 3),
-            "unit": ("V-cycles/s (fixed 1.5M-row graph)" if g3 else
-                     "V-cycles/s (256^3-equivalent: rows*cycles/s / 256^3)"),
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt * 1e3 / args.steps, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if g3 else "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": ("synthetic (b = A x*, x* splitmix64 U(-1,1) seed 42, x0 = 0)" +
-                     ("; matrix: seeded graph-Laplacian SUBSTITUTE for SuiteSparse G3_circuit "
-                      "(not available offline)" if g3 else "")),
-            "config": {
-                "workload": (f"G3_circuit substitute: graph Laplacian on a {grid[0]}x{grid[1]} lattice "
-                             f"({n_global} rows, {infos[0]['nnz_global']} nnz, seed 1), "
-                             f"{'random numbering' if args.no_reorder else 'RCM-reordered'}, smoothed "
-                             f"aggregation (MIS(2)), hybrid GS(64) 1+1 V-cycle, {part_label}" +
-                             (f", coarse drop tolerance {drop_tol:g}" if drop_tol else ""))
-                if g3 else
-                (f"3D 27-pt Q1 anisotropic diffusion (1,1,1e-3) {grid[0]}x{grid[1]}x{grid[2]}, "
-                             f"smoothed aggregation (MIS(2)), hybrid GS(64) 1+1 V-cycle, {part_label}" +
-                             (f", coarse drop tolerance {drop_tol:g}" if drop_tol else ""))
-                if sa27 else
-                (f"3D 7-pt Poisson {grid[0]}x{grid[1]}x{grid[2]}, PMIS + "
-                 f"{'classical' if args.interp == 'classical' else 'extended+i (P_max 4)'} interp, "
-                 f"Jacobi(2/3) 1+1 V-cycle, {part_label}" +
-                 (f", coarse drop tolerance {drop_tol:g} (non-Galerkin)" if drop_tol else "")),
-                "grid": list(grid),
-                "global_rows": n_global,
-                "levels": nlev,
-                "level_rows": [i["n_global"] for i in infos],
-                "level_nnz": [i["nnz_global"] for i in infos],
-                "operator_complexity": round(sum(i["nnz_global"] for i in infos) / infos[0]["nnz_global"], 3),
-                # the densest coarse level's mean nonzeros per row
-                "coarse_nnz_per_row_max": max((round(i["nnz_global"] / max(1, i["n_global"]), 1)
-                                               for i in infos[1:]), default=None),
-                "drop_tol": drop_tol,
-                "parallelism": f"row-partition x{world}, RCCL halo",
-                "partition": part_label,
-                "setup_s": round(setup_s, 2),
-                "reorder_s": None if reorder_s is None else round(reorder_s, 2),
-                "hipgraph": graph_used,
-                "hipgraph_all_ranks": graph_all,  # the timed mode (the probe's choice at N > 1)
-                "graph_available": graph_avail,
-                "gs_split_per_rank_level": gs_split,
-            },
-            "iters_per_s": round(iters_per_s, 3),
-            "convergence_factor": conv,
-            "convergence_factor_last5": conv_last5,
+            **head,
             # bytes one cycle streams in the stored formats (<= peak x time) and the plain-CSR
             # count of SURVEY.md 8(d) (what a CSR implementation of the same cycle would move)
             "vcycle_stored_bytes": cyc_stored,
@@ -668,6 +710,29 @@ def main():
     del ml, A
     if world > 1:
         comm.close()
+
+
+def dump_outputs(path, x, hist, rank, world):
+    """--dump-outputs: what the timed solve returned, as float64 .npy files under `path`.
+
+    residual_history.npy: the residual norms before the first and after every timed cycle
+    (rank 0 writes it; it is the global norm).  x.npy: this rank's rows of the iterate after
+    the last cycle (x_rank<r>.npy over several ranks) when everything fits DUMP_CAP_BYTES;
+    else x_sample.npy holds DUMP_SAMPLE / world of its entries, drawn without replacement by a
+    generator seeded with DUMP_SEED, and x_sample_index.npy their (sorted) local row numbers."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    if rank == 0:
+        np.save(os.path.join(path, "residual_history.npy"), np.asarray(hist, np.float64))
+    if world * x.nbytes + 8 * len(hist) <= DUMP_CAP_BYTES:
+        np.save(os.path.join(path, f"x{tag}.npy"), x)
+        return
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, min(x.size, DUMP_SAMPLE // world),
+                                                          replace=False))
+    np.save(os.path.join(path, f"x_sample{tag}.npy"), x[idx])
+    np.save(os.path.join(path, f"x_sample_index{tag}.npy"), idx.astype(np.float64))
 
 
 def kernel_name(info, op):

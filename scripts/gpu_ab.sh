@@ -1,14 +1,14 @@
 #!/bin/bash
 # Same-box A/B: the default library and an alternative build (RAPTOR_AMD_LIB=$ALT) on the bench
-# configs in $CONFIGS; bench lines under gpurun_out/${R}_{default,alt}_{cfg}.json.
+# configs in $CONFIGS; bench lines under $OUT/${R}_{default,alt}_{cfg}.json.
 set -o pipefail
-cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out; export TMPDIR=/tmp
+cd "$(dirname "$0")/.."; OUT=${OUT:-bench_out}; mkdir -p $OUT; export TMPDIR=/tmp
 R=${ROUND:-ab}
 for cfg in ${CONFIGS:-7pt}; do
   for v in default alt; do
-    if [ $v = alt ]; then export RAPTOR_AMD_LIB=$GRAFT_REPO_ROOT/$ALT; else unset RAPTOR_AMD_LIB; fi
-    timeout -k 10 400 python bench.py --config $cfg --no-cpu-baseline $BENCH_ARGS > gpurun_out/${R}_${v}_${cfg}.json 2> gpurun_out/${R}_${v}_${cfg}.err || { tail gpurun_out/${R}_${v}_${cfg}.err; exit 1; }
-    python - "$v" "$cfg" gpurun_out/${R}_${v}_${cfg}.json <<'PY'
+    if [ $v = alt ]; then export RAPTOR_AMD_LIB=$PWD/$ALT; else unset RAPTOR_AMD_LIB; fi
+    timeout -k 10 400 python bench.py --full --config $cfg --no-cpu-baseline $BENCH_ARGS > $OUT/${R}_${v}_${cfg}.json 2> $OUT/${R}_${v}_${cfg}.err || { tail $OUT/${R}_${v}_${cfg}.err; exit 1; }
+    python - "$v" "$cfg" $OUT/${R}_${v}_${cfg}.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[3]))
 t = " ".join(f"L{k['level']}:{k['op'].split()[0]}={k['us']}" for k in d["vcycle_kernels"])
