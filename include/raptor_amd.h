@@ -208,7 +208,7 @@ int amg_par_csr_destroy(amg_matrix A);
 #define AMG_SMOOTH_HYBRID_GS 1
 #define AMG_INTERP_CLASSICAL 0  /* RS / PMIS: distance-one classical (modified) interpolation  */
 #define AMG_INTERP_EXT_I 1      /* RS / PMIS: distance-two extended+i with P_max truncation    *
-                                 * (one rank)                                    */
+                                 * (any number of ranks; PMIS: built on the GPU) */
 
 typedef struct amg_options {
     int32_t coarsen;
@@ -227,7 +227,8 @@ typedef struct amg_options {
     int64_t replicate_below;  /* multi-rank: levels with <= this many global rows are held
                                  whole by every rank and cycled without communication (one
                                  allgather of b per cycle); 0 = never.  Default 262144.     */
-    int32_t interp;           /* RS / PMIS: AMG_INTERP_CLASSICAL (default) or AMG_INTERP_EXT_I */
+    int32_t interp;           /* RS / PMIS: AMG_INTERP_CLASSICAL (default) or AMG_INTERP_EXT_I
+                                 (distance two; states fetched two halos deep on several ranks) */
     int32_t p_max;            /* AMG_INTERP_EXT_I: interpolation entries kept per row (the
                                  largest |w|, rescaled to the row sum); 0 = all.  Default 4  */
     double drop_tol;          /* coarse-operator drop tolerance (non-Galerkin): off-diagonals of
@@ -262,6 +263,14 @@ int amg_solver_level_matrix(amg_solver S, int32_t level, int32_t which, amg_matr
 /* Integer setup result of level l for the local rows: C/F marker (1 = C, 0 = F) for
  * RS/PMIS, global aggregate id for SA.  Bit-exact against the oracle. */
 int amg_solver_level_split(amg_solver S, int32_t level, int32_t* out_local);
+/* 1: level l's split and P were built by the device setup path; 0: by the host path
+ * (Ruge-Stueben's serial first pass, setup_device == 0 or 2).  l < num_levels - 1. */
+int amg_solver_level_setup_device(amg_solver S, int32_t level, int32_t* out);
+/* Diagnostics of the device extended+i interpolation of level l (zeros where another path built
+ * the level): *scratch_rows = this rank's rows whose candidate set or strong-neighbour list
+ * exceeded the per-wavefront LDS capacity and were built through global scratch; *launches =
+ * kernel launches the count pass split the rows into.  l < num_levels - 1. */
+int amg_solver_level_ext_stats(amg_solver S, int32_t level, int64_t* scratch_rows, int64_t* launches);
 /* One V-cycle x <- cycle(x, b) (ParMultilevel::cycle). */
 int amg_solver_cycle(amg_solver S, double* x, const double* b);
 /* ParMultilevel::solve: r0 = ||b-Ax||; up to max_iter cycles until ||r||/r0 < tol.

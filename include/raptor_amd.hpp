@@ -184,6 +184,18 @@ public:
         check(amg_solver_level_split(h_, level, s.data()));
         return s;
     }
+    // true: level's split and P came from the device setup path (not the host fallback)
+    bool level_setup_on_device(int level) const {
+        int32_t v = 0;
+        check(amg_solver_level_setup_device(h_, level, &v));
+        return v != 0;
+    }
+    // device extended+i diagnostics: {rows built through global scratch, count-pass launches}
+    std::pair<int64_t, int64_t> level_ext_stats(int level) const {
+        int64_t r = 0, n = 0;
+        check(amg_solver_level_ext_stats(h_, level, &r, &n));
+        return {r, n};
+    }
     void set_graph(bool on) { check(amg_solver_set_graph(h_, on ? 1 : 0)); }
     bool graph() const {
         int32_t v = 0;

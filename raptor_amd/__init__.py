@@ -586,7 +586,8 @@ class ParMultilevel:
 
     ``coarsen``: "rs" (serial Ruge-Stueben), "pmis", or "sa" (smoothed aggregation over MIS(2)
     aggregates).  ``smoother``: "jacobi" or "hybrid_gs".  ``interp`` (RS / PMIS): "classical"
-    (distance one) or "ext+i" (distance two, ``p_max`` entries kept per row; one rank).
+    (distance one) or "ext+i" (distance two, ``p_max`` entries kept per row; any number of
+    ranks, built on the GPU under PMIS).
     ``drop_tol`` > 0: coarse operators lose their off-diagonals below drop_tol sqrt(|a_ii a_jj|),
     lumped onto the diagonal (non-Galerkin)."""
 
@@ -646,6 +647,22 @@ class ParMultilevel:
         check(lib().amg_solver_level_split(self.h, int(level),
                                            out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
+
+    def level_setup_on_device(self, level: int) -> int:
+        """1 if the level's split and P were built by the device setup path, 0 if the host
+        path built them (Ruge-Stueben, ``setup_device`` 0 or 2).  ``level < num_levels - 1``."""
+        v = C.c_int32()
+        check(lib().amg_solver_level_setup_device(self.h, int(level), C.byref(v)))
+        return v.value
+
+    def level_ext_stats(self, level: int) -> dict:
+        """Diagnostics of the device extended+i interpolation of a level: ``scratch_rows`` (this
+        rank's rows built through global scratch because they exceed the per-wavefront LDS
+        capacity) and ``launches`` (kernel launches of the count pass); zeros where another
+        path built the level."""
+        r, n = C.c_int64(), C.c_int64()
+        check(lib().amg_solver_level_ext_stats(self.h, int(level), C.byref(r), C.byref(n)))
+        return {"scratch_rows": r.value, "launches": n.value}
 
     def set_graph(self, enable: bool):
         """Replay captured hipGraphs (True) or launch cycles eagerly (False).  Collective."""
@@ -714,7 +731,8 @@ class ParMultilevel:
 
 class ParRugeStubenSolver(ParMultilevel):
     """Classical AMG: strength theta = 0.25, RS (serial) or PMIS coarsening, classical
-    interpolation, Jacobi smoothing."""
+    interpolation or ``interp="ext+i"`` (extended+i with P_max truncation, any number of ranks;
+    with PMIS every level's setup runs on the GPU), Jacobi smoothing."""
 
     def __init__(self, coarsen="pmis", **kw):
         if coarsen not in ("rs", "pmis"):

@@ -145,6 +145,8 @@ SIGNATURES = {
     "amg_solver_level_info": (C.c_int, [_vp, _i32, C.POINTER(LevelInfo)]),
     "amg_solver_level_matrix": (C.c_int, [_vp, _i32, _i32, C.POINTER(_vp)]),
     "amg_solver_level_split": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "amg_solver_level_setup_device": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "amg_solver_level_ext_stats": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
     "amg_solver_cycle": (C.c_int, [_vp, _vp, _vp]),
     "amg_solver_solve": (C.c_int, [_vp, _vp, _vp, _i32, _f64, _pf64, C.POINTER(_i32)]),
     "amg_solver_pcg": (C.c_int, [_vp, _vp, _vp, _i32, _f64, _pf64, C.POINTER(_i32)]),

@@ -644,6 +644,24 @@ int amg_solver_level_split(amg_solver S, int32_t l, int32_t* out) {
     });
 }
 
+int amg_solver_level_setup_device(amg_solver S, int32_t l, int32_t* out) {
+    return guard([&] {
+        AMG_CHECK(S && out, "null argument");
+        AMG_CHECK(l >= 0 && l + 1 < (int32_t)S->s.levels.size(), "level has no splitting");
+        *out = (size_t)l < S->s.level_on_device.size() ? S->s.level_on_device[l] : 0;
+    });
+}
+
+int amg_solver_level_ext_stats(amg_solver S, int32_t l, int64_t* scratch_rows, int64_t* launches) {
+    return guard([&] {
+        AMG_CHECK(S && scratch_rows && launches, "null argument");
+        AMG_CHECK(l >= 0 && l + 1 < (int32_t)S->s.levels.size(), "level has no splitting");
+        const bool have = (size_t)l < S->s.level_ext_stats.size();
+        *scratch_rows = have ? S->s.level_ext_stats[l][0] : 0;
+        *launches = have ? S->s.level_ext_stats[l][1] : 0;
+    });
+}
+
 int amg_solver_cycle(amg_solver S, double* x, const double* b) {
     return guard([&] {
         AMG_CHECK(S, "null solver");

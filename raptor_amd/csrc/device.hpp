@@ -5,6 +5,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <initializer_list>
 #include <memory>
 #include <string>
@@ -212,10 +213,12 @@ void build_formats_device(DevMatrix& M, const std::vector<int>& hrp, const hvec<
 HostCSR galerkin_device(Context& ctx, const HostComm& comm, const HostCSR& R, const HostCSR& A,
                         const HostCSR& P, SetupImages* imgs = nullptr);
 // device setup of one level (setup_device.hip): strength, PMIS or MIS(2) aggregation,
-// classical or smoothed-aggregation P; false where it does not apply.  imgs: A's device image,
-// P registered (SA: one rank)
+// classical, extended+i or smoothed-aggregation P; false where it does not apply.  imgs: A's
+// device image, P registered (SA: one rank).  ext_stats (extended+i, else zeros): [0] this
+// rank's rows built through the global-scratch path, [1] count-pass launches of the LDS form
 bool level_setup_device(Context& ctx, const HostComm& comm, const HostCSR& A, const amg_options& opt,
-                        int level, HostCSR& P, std::vector<int32_t>& split, SetupImages* imgs = nullptr);
+                        int level, HostCSR& P, std::vector<int32_t>& split, SetupImages* imgs = nullptr,
+                        int64_t* ext_stats = nullptr);
 bool transpose_device(Context& ctx, const HostComm& comm, const HostCSR& P, HostCSR& R,
                       SetupImages* imgs = nullptr);
 // coarse-operator drop tolerance (host_setup.cpp sparsify) on A's device image (one rank; the
@@ -548,6 +551,10 @@ struct Solver {
     Context* ctx = nullptr;
     amg_options opt{};
     std::vector<Level> levels;
+    // per level with a splitting: 1 if level_setup_device built it, 0 if the host path did
+    std::vector<int32_t> level_on_device;
+    // per level, extended+i on the device: {rows of the scratch path, LDS-form launches}
+    std::vector<std::array<int64_t, 2>> level_ext_stats;
     DevMatrix* A0 = nullptr;  // borrowed fine matrix (levels[0].A is null)
     // coarsest level: dense inverse rows of this rank, row-major (invT[i * n + j]); b gathered
     // padded, then unpadded into global order (bfull)

@@ -172,8 +172,35 @@ std::vector<int32_t> rs_split(const HostComm& comm, const HostCSR& S);
 std::vector<int32_t> pmis_split(const HostComm& comm, const HostCSR& S, uint64_t seed);
 HostCSR interp_classical(const HostComm& comm, const HostCSR& A, const HostCSR& S,
                          const std::vector<int32_t>& cf);
+// the classical strength test of one row (global id g; len entries c / v): m = max over the
+// off-diagonal entries of -a (the first one sets it), no strong entry if m <= 0, else entry
+// (c, v) is strong iff c != g and -v >= theta m.  strength_classical() and interp_ext_i()'s
+// S_k of a ghost row k both run this, so an owner's S row and its recomputation are the same set
+struct StrongTest {
+    bool has;
+    double thr;
+    int64_t g;
+    bool operator()(int64_t c, double v) const { return has && c != g && -v >= thr; }
+};
+inline StrongTest classical_strong_test(const int64_t* c, const double* v, int64_t len, int64_t g, double theta) {
+    double mx = 0.0;
+    bool any = false;
+    for (int64_t k = 0; k < len; ++k) {
+        if (c[k] == g) continue;
+        const double m = -v[k];
+        if (!any || m > mx) mx = m;
+        any = true;
+    }
+    return StrongTest{any && mx > 0.0, theta * mx, g};
+}
+// extended+i on any number of ranks: rows of the strong F neighbours one halo deep, the states
+// and coarse ids of their strong neighbours two halos deep; theta is S's threshold (S_k of a
+// ghost row k is recomputed from the row)
 HostCSR interp_ext_i(const HostComm& comm, const HostCSR& A, const HostCSR& S, const std::vector<int32_t>& cf,
-                     int p_max);
+                     int p_max, double theta);
+// the halo of extended+i's state lookups: the off-rank columns of the local rows and of the
+// ghost rows G of plan (A's one-deep halo)
+HaloPlan ext_state_plan(const HostComm& comm, const HostCSR& A, const HaloPlan& plan, const GhostRows& G);
 // returns global aggregate id per local row; *n_agg_global receives the count
 std::vector<int64_t> mis2_aggregate(const HostComm& comm, const HostCSR& S, uint64_t seed,
                                     int64_t* n_agg_global, std::vector<int64_t>* agg_starts);

@@ -66,24 +66,12 @@ static HostCSR filter_rows(const HostCSR& A, F keep) {
 // classical: m_i = max_{j != i} (-a_ij); none if m_i <= 0; strong iff -a_ij >= theta*m_i
 HostCSR strength_classical(const HostComm& comm, const HostCSR& A, double theta) {
     int64_t n = A.nrows(), lo = A.row_starts[comm.rank];
-    std::vector<double> thr(n);
-    std::vector<uint8_t> has(n);
+    std::vector<StrongTest> test(n);
 #pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < n; ++i) {
-        double mx = 0.0;
-        bool any = false;
-        for (int64_t k = A.rp[i]; k < A.rp[i + 1]; ++k) {
-            if (A.col[k] == lo + i) continue;
-            double v = -A.val[k];
-            if (!any || v > mx) mx = v;
-            any = true;
-        }
-        has[i] = any && mx > 0.0;
-        thr[i] = theta * mx;
-    }
-    return filter_rows(A, [&](int64_t i, int64_t k) {
-        return has[i] && A.col[k] != lo + i && -A.val[k] >= thr[i];
-    });
+    for (int64_t i = 0; i < n; ++i)
+        test[i] = classical_strong_test(A.col.data() + A.rp[i], A.val.data() + A.rp[i], A.rp[i + 1] - A.rp[i],
+                                        lo + i, theta);
+    return filter_rows(A, [&](int64_t i, int64_t k) { return test[i](A.col[k], A.val[k]); });
 }
 
 // SA, signed (r6): -a_ij >= theta * sqrt(|a_ii * a_jj|), j != i (sa_strong)
@@ -316,110 +304,199 @@ std::vector<int32_t> pmis_split(const HostComm& comm, const HostCSR& S, uint64_t
 // Classical (modified) interpolation, distance 1.  See the oracle for the formula.
 // --------------------------------------------------------------------------------
 // Extended+i interpolation (r6 option; oracle orc_interp_ext_i): distance two,
-// P_max truncation.  One rank (the distance-two sets need the rows of strong F neighbours and
-// their strong C neighbours' states, which a multi-rank setup would fetch two halos deep).
+// P_max truncation, on any number of ranks.  A strong F neighbour k of a local row is a column
+// of that row: its A row is local or a ghost row of A's one-deep halo, and S_k of a ghost row
+// is recomputed from it (classical_strong_test, the test S was built with).  The members of
+// S_k may lie two halos deep: their states and coarse ids come through ext_state_plan().
+// Scratch is row-local (the sorted C^_i and one accumulator per member), so a thread's memory
+// does not grow with n.  Precondition: the rows of A and S (and so the ghost rows) hold
+// ascending, distinct column ids -- the row-local lookups are binary searches (is_strong over
+// S_i, in_list over C^_i), where the earlier marker vectors took any order.  HostCSR keeps
+// rows that way (host.hpp), and strength_classical keeps A's order.
+HaloPlan ext_state_plan(const HostComm& comm, const HostCSR& A, const HaloPlan& plan, const GhostRows& G) {
+    const int64_t lo = A.col_starts[comm.rank], hi = A.col_starts[comm.rank + 1];
+    std::vector<int64_t> need(plan.halo_gid);
+    for (int64_t c : G.col)
+        if (c < lo || c >= hi) need.push_back(c);
+    return build_halo_plan(comm, A.col_starts, std::move(need));
+}
+
 HostCSR interp_ext_i(const HostComm& comm, const HostCSR& A, const HostCSR& S, const std::vector<int32_t>& cf,
-                     int p_max) {
-    AMG_CHECK(comm.nranks == 1, "extended+i interpolation is implemented for one rank");
-    const int64_t n = A.nrows();
-    std::vector<int64_t> cmap(n);
-    int64_t nc = 0;
-    for (int64_t i = 0; i < n; ++i) cmap[i] = cf[i] == ST_C ? nc++ : -1;
-    const std::vector<double> diag = diagonal(comm, A);
-    std::vector<std::vector<int64_t>> pcol(n);
-    std::vector<std::vector<double>> pval(n);
+                     int p_max, double theta) {
+    const int64_t n = A.nrows(), lo = A.row_starts[comm.rank], hi = A.row_starts[comm.rank + 1];
+    int64_t ncl = 0;
+    for (int32_t v : cf) ncl += v == ST_C;
+    std::vector<int64_t> counts = comm.allgather(ncl);
+    std::vector<int64_t> cstarts(comm.nranks + 1, 0);
+    for (int r = 0; r < comm.nranks; ++r) cstarts[r + 1] = cstarts[r] + counts[r];
+    std::vector<int64_t> cmap(n, -1);
+    for (int64_t i = 0, c = cstarts[comm.rank]; i < n; ++i)
+        if (cf[i] == ST_C) cmap[i] = c++;
+    HaloPlan plan = halo_plan_for_cols(comm, A);
+    GhostRows G = fetch_rows(comm, plan, A);
+    HaloPlan splan = ext_state_plan(comm, A, plan, G);
+    std::vector<int32_t> hcf(splan.n_halo());
+    std::vector<int64_t> hcmap(splan.n_halo());
+    splan.forward(comm, cf.data(), hcf.data());
+    splan.forward(comm, cmap.data(), hcmap.data());
+
+    HostCSR P;
+    P.n_global_rows = A.n_global_rows;
+    P.n_global_cols = cstarts[comm.nranks];
+    P.row_starts = A.row_starts;
+    P.col_starts = cstarts;
+    // rows go to the threads in chunks of kChunk, handed out dynamically (a few very long rows
+    // -- hubs, Galerkin levels -- would unbalance contiguous blocks); chunk t keeps its own
+    // output, concatenated in chunk order below
+    const int64_t kChunk = 1024, nt = (n + kChunk - 1) / kChunk;
+    std::vector<std::vector<int64_t>> tcol(nt), tlen(nt);
+    std::vector<std::vector<double>> tval(nt);
 #pragma omp parallel
     {
-        std::vector<int64_t> strong(n, -1), inC(n, -1), list;
-        std::vector<double> num(n), w;
+        std::vector<int64_t> list;  // C^_i, global ids ascending
+        std::vector<double> num, w;
         std::vector<char> keep;
-#pragma omp for schedule(dynamic, 1024)
-        for (int64_t i = 0; i < n; ++i) {
+        auto state = [&](int64_t g, int64_t* cm) -> int32_t {
+            if (g >= lo && g < hi) {
+                if (cm) *cm = cmap[g - lo];
+                return cf[g - lo];
+            }
+            int64_t h = splan.find(g);
+            if (cm) *cm = hcmap[h];
+            return hcf[h];
+        };
+        // row g of A: local, or the ghost row of a halo point
+        auto arow = [&](int64_t g, const int64_t*& rc, const double*& rv, int64_t& rl) {
+            if (g >= lo && g < hi) {
+                int64_t r = g - lo;
+                rc = &A.col[A.rp[r]], rv = &A.val[A.rp[r]], rl = A.rp[r + 1] - A.rp[r];
+            } else {
+                int64_t h = plan.find(g);
+                rc = &G.col[G.rp[h]], rv = &G.val[G.rp[h]], rl = G.rp[h + 1] - G.rp[h];
+            }
+        };
+        auto in_list = [&](int64_t g) -> int64_t {
+            auto it = std::lower_bound(list.begin(), list.end(), g);
+            return it != list.end() && *it == g ? (int64_t)(it - list.begin()) : -1;
+        };
+#pragma omp for schedule(dynamic, 1)
+        for (int64_t t = 0; t < nt; ++t)
+        for (int64_t i = t * kChunk; i < std::min(n, (t + 1) * kChunk); ++i) {
+            const int64_t gi = lo + i;
             if (cf[i] == ST_C) {
-                pcol[i].push_back(cmap[i]);
-                pval[i].push_back(1.0);
+                tcol[t].push_back(cmap[i]);
+                tval[t].push_back(1.0);
+                tlen[t].push_back(1);
                 continue;
             }
+            const int64_t* sb = S.col.data() + S.rp[i];
+            const int64_t* se = S.col.data() + S.rp[i + 1];
+            auto is_strong = [&](int64_t g) { return std::binary_search(sb, se, g); };
             list.clear();
-            for (int64_t t = S.rp[i]; t < S.rp[i + 1]; ++t) strong[S.col[t]] = i;
-            for (int64_t t = S.rp[i]; t < S.rp[i + 1]; ++t) {
-                const int64_t j = S.col[t];
-                if (cf[j] == ST_C && inC[j] != i) inC[j] = i, list.push_back(j), num[j] = 0.0;
-            }
-            for (int64_t t = S.rp[i]; t < S.rp[i + 1]; ++t) {
-                const int64_t k = S.col[t];
-                if (cf[k] == ST_C) continue;
-                for (int64_t u = S.rp[k]; u < S.rp[k + 1]; ++u) {
-                    const int64_t j = S.col[u];
-                    if (cf[j] == ST_C && inC[j] != i) inC[j] = i, list.push_back(j), num[j] = 0.0;
+            for (const int64_t* p = sb; p < se; ++p) {
+                const int64_t k = *p;
+                if (state(k, nullptr) == ST_C) {
+                    list.push_back(k);
+                    continue;
+                }
+                if (k >= lo && k < hi) {
+                    for (int64_t u = S.rp[k - lo]; u < S.rp[k - lo + 1]; ++u)
+                        if (state(S.col[u], nullptr) == ST_C) list.push_back(S.col[u]);
+                } else {
+                    const int64_t* rc;
+                    const double* rv;
+                    int64_t rl;
+                    arow(k, rc, rv, rl);
+                    const StrongTest st = classical_strong_test(rc, rv, rl, k, theta);
+                    for (int64_t u = 0; u < rl; ++u)
+                        if (st(rc[u], rv[u]) && state(rc[u], nullptr) == ST_C) list.push_back(rc[u]);
                 }
             }
-            double d = diag[i];
+            std::sort(list.begin(), list.end());
+            list.erase(std::unique(list.begin(), list.end()), list.end());
+            const int64_t m = (int64_t)list.size();
+            num.assign(m, 0.0);
+            double d = 0.0;
+            for (int64_t k = A.rp[i]; k < A.rp[i + 1]; ++k)
+                if (A.col[k] == gi) {
+                    d = A.val[k];
+                    break;
+                }
             for (int64_t k = A.rp[i]; k < A.rp[i + 1]; ++k) {
                 const int64_t j = A.col[k];
-                if (j == i) continue;
-                if (inC[j] == i) num[j] += A.val[k];
-                else if (strong[j] != i) d += A.val[k];
+                if (j == gi) continue;
+                const int64_t q = in_list(j);
+                if (q >= 0) num[q] += A.val[k];
+                else if (!is_strong(j)) d += A.val[k];
             }
             for (int64_t k = A.rp[i]; k < A.rp[i + 1]; ++k) {
                 const int64_t kk = A.col[k];
-                if (kk == i || strong[kk] != i || cf[kk] == ST_C) continue;
-                const bool pos = diag[kk] > 0.0;
+                if (kk == gi || !is_strong(kk) || state(kk, nullptr) == ST_C) continue;
+                const int64_t* rc;
+                const double* rv;
+                int64_t rl;
+                arow(kk, rc, rv, rl);
+                double akk = 0.0;
+                for (int64_t u = 0; u < rl; ++u)
+                    if (rc[u] == kk) {
+                        akk = rv[u];
+                        break;
+                    }
+                const bool pos = akk > 0.0;
                 auto abar = [pos](double v) { return pos ? v < 0.0 : v > 0.0; };
                 double sk = 0.0;
-                for (int64_t u = A.rp[kk]; u < A.rp[kk + 1]; ++u) {
-                    const int64_t l = A.col[u];
-                    if (abar(A.val[u]) && (inC[l] == i || l == i)) sk += A.val[u];
-                }
+                for (int64_t u = 0; u < rl; ++u)
+                    if (abar(rv[u]) && (rc[u] == gi || in_list(rc[u]) >= 0)) sk += rv[u];
                 if (sk == 0.0) {
                     d += A.val[k];
                     continue;
                 }
-                for (int64_t u = A.rp[kk]; u < A.rp[kk + 1]; ++u) {
-                    const int64_t l = A.col[u];
-                    if (!abar(A.val[u])) continue;
-                    if (inC[l] == i) num[l] += (A.val[k] * A.val[u]) / sk;
-                    else if (l == i) d += (A.val[k] * A.val[u]) / sk;
+                for (int64_t u = 0; u < rl; ++u) {
+                    if (!abar(rv[u])) continue;
+                    const int64_t q = in_list(rc[u]);
+                    if (q >= 0) num[q] += (A.val[k] * rv[u]) / sk;
+                    else if (rc[u] == gi) d += (A.val[k] * rv[u]) / sk;
                 }
             }
-            std::sort(list.begin(), list.end());
-            const int64_t m = (int64_t)list.size();
             w.resize(m);
             keep.assign(m, 1);
-            for (int64_t t = 0; t < m; ++t) w[t] = -num[list[t]] / d;
+            for (int64_t q = 0; q < m; ++q) w[q] = -num[q] / d;
             if (p_max > 0 && m > p_max) {
                 double tot = 0.0, kept = 0.0;
-                for (int64_t t = 0; t < m; ++t) tot += w[t], keep[t] = 0;
+                for (int64_t q = 0; q < m; ++q) tot += w[q], keep[q] = 0;
                 for (int r = 0; r < p_max; ++r) {
                     int64_t best = -1;
-                    for (int64_t t = 0; t < m; ++t)
-                        if (!keep[t] && (best < 0 || std::fabs(w[t]) > std::fabs(w[best]))) best = t;
+                    for (int64_t q = 0; q < m; ++q)
+                        if (!keep[q] && (best < 0 || std::fabs(w[q]) > std::fabs(w[best]))) best = q;
                     keep[best] = 1;
                 }
-                for (int64_t t = 0; t < m; ++t)
-                    if (keep[t]) kept += w[t];
+                for (int64_t q = 0; q < m; ++q)
+                    if (keep[q]) kept += w[q];
                 if (kept != 0.0) {
                     const double f = tot / kept;
-                    for (int64_t t = 0; t < m; ++t)
-                        if (keep[t]) w[t] = w[t] * f;
+                    for (int64_t q = 0; q < m; ++q)
+                        if (keep[q]) w[q] = w[q] * f;
                 }
             }
-            for (int64_t t = 0; t < m; ++t)
-                if (keep[t]) pcol[i].push_back(cmap[list[t]]), pval[i].push_back(w[t]);
+            int64_t len = 0;
+            for (int64_t q = 0; q < m; ++q) {
+                if (!keep[q]) continue;
+                int64_t cm;
+                state(list[q], &cm);
+                tcol[t].push_back(cm);
+                tval[t].push_back(w[q]);
+                ++len;
+            }
+            tlen[t].push_back(len);
         }
     }
-    HostCSR P;
-    P.n_global_rows = n;
-    P.n_global_cols = nc;
-    P.row_starts = A.row_starts;
-    P.col_starts = {0, nc};
     P.rp.assign(n + 1, 0);
-    for (int64_t i = 0; i < n; ++i) P.rp[i + 1] = P.rp[i] + (int64_t)pcol[i].size();
-    P.col.resize(P.rp[n]);
-    P.val.resize(P.rp[n]);
-    for (int64_t i = 0; i < n; ++i) {
-        std::copy(pcol[i].begin(), pcol[i].end(), P.col.begin() + P.rp[i]);
-        std::copy(pval[i].begin(), pval[i].end(), P.val.begin() + P.rp[i]);
+    int64_t r = 0;
+    for (int64_t t = 0; t < nt; ++t)
+        for (int64_t l : tlen[t]) P.rp[r + 1] = P.rp[r] + l, ++r;
+    for (int64_t t = 0; t < nt; ++t) {
+        P.col.insert(P.col.end(), tcol[t].begin(), tcol[t].end());
+        P.val.insert(P.val.end(), tval[t].begin(), tval[t].end());
     }
     return P;
 }
@@ -831,7 +908,7 @@ void build_hierarchy(const HostComm& comm, const HostCSR& A0, const amg_options&
             split = opt.coarsen == AMG_COARSEN_RS ? rs_split(comm, S)
                                                   : pmis_split(comm, S, opt.seed + (uint64_t)l);
             tm.lap(L + "split");
-            P = opt.interp == AMG_INTERP_EXT_I ? interp_ext_i(comm, A, S, split, opt.p_max)
+            P = opt.interp == AMG_INTERP_EXT_I ? interp_ext_i(comm, A, S, split, opt.p_max, opt.strong_threshold)
                                                : interp_classical(comm, A, S, split);
             tm.lap(L + "interpolation");
         } else {

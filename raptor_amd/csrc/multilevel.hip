@@ -213,6 +213,8 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
     ctx = A.ctx;
     opt = o;
     A0 = &A;
+    level_on_device.clear();
+    level_ext_stats.clear();
 
     const HostComm& comm = ctx->host;
     HostHierarchy H;
@@ -244,7 +246,15 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
         // 2: Galerkin products only (the round-1 split, for A/B and tests)
         if (opt.setup_device == 1) {
             level_fn = [this, &comm, im](int l, const HostCSR& A, HostCSR& P, std::vector<int32_t>& split) {
-                return level_setup_device(*ctx, comm, A, opt, l, P, split, im);
+                int64_t st[2] = {0, 0};
+                const bool dev = level_setup_device(*ctx, comm, A, opt, l, P, split, im, st);
+                if (level_on_device.size() <= (size_t)l) {
+                    level_on_device.resize((size_t)l + 1, 0);
+                    level_ext_stats.resize((size_t)l + 1, {0, 0});
+                }
+                level_on_device[l] = dev ? 1 : 0;
+                level_ext_stats[l] = {st[0], st[1]};
+                return dev;
             };
             transpose_fn = [this, &comm, im](const HostCSR& P, HostCSR& R) {
                 return transpose_device(*ctx, comm, P, R, im);

@@ -1,9 +1,9 @@
 // setup_device.hip -- AMG setup on the GPU: strength of connection,
-// PMIS splitting, classical interpolation, MIS(2) aggregation and the smoothed-aggregation
-// prolongator on any number of ranks, the transpose R = P^T on one rank.  Every integer
-// decision and every floating-point sum follows host_setup.cpp / oracle/amg_oracle.c exactly
-// (DESIGN.md 3), so the hierarchy is bit-identical to the host path's at every rank count;
-// the Galerkin products stay on the device SpGEMM (spgemm.hip).
+// PMIS splitting, classical and extended+i interpolation, MIS(2) aggregation and the
+// smoothed-aggregation prolongator on any number of ranks, the transpose R = P^T on one
+// rank.  Every integer decision and every floating-point sum follows host_setup.cpp /
+// oracle/amg_oracle.c exactly, so the hierarchy is bit-identical to the host
+// path's at every rank count; the Galerkin products stay on the device SpGEMM (spgemm.hip).
 //
 // Layout: one upload of this rank's rows of A per level -- int32 row_ptr, int32 GLOBAL column
 // ids, fp64 values; the strength graph S stays on the device; per-row kernels are one thread
@@ -523,6 +523,334 @@ __global__ __launch_bounds__(64 * kIwWaves) void interp_wave_kernel(ARows R, DCs
         }
         qbase += __popcll(m);
     }
+}
+
+// ---- extended+i interpolation -----------------------------------------------------------
+// host_setup.cpp interp_ext_i(), one wavefront per F row:
+//  * gather: the C members of S_i and of S_k for every strong F neighbour k (local k: its S
+//    row; ghost k: the classical strength test recomputed from the ghost row) go into a hash
+//    set, which drops duplicates as they arrive; the set is compacted and rank-sorted into the
+//    ascending list C^_i (ascending fine ids = ascending coarse ids);
+//  * the count pass ends there: min(|C^_i|, p_max) entries;
+//  * s_k: one strong neighbour per lane, a serial sum in row k's order;
+//  * d: lane 0, the host's order (a_ii, the weak entries outside C^_i in row order, the strong
+//    F neighbours in row order);
+//  * num_j: one member of C^_i per lane: a_ij, then (a_ik a_kj) / s_k in row order of k;
+//  * truncation: lane 0 runs the host's loops on the weights in LDS.
+// The set, the list, s_k and the weights live in LDS (kExtCap members and kExtCap strong
+// neighbours per wave).  A row with more of either is listed in the count pass and runs the
+// same code with its tables in global scratch sized from the row's own bound (ExtSlot).
+// State lookups go through D2, the halo of ext_state_plan() (two deep); rows through R.
+constexpr int kExtWaves = 4, kExtCap = 256, kExtTab = 2 * kExtCap;
+enum { EX_F = 1, EX_POS = 2 };
+
+struct ExtArgs {
+    ARows R;
+    DCsr S;
+    Dist D2;
+    const int* cf;
+    const int* hcf;
+    const int* cmap;
+    const int* hcmap;
+    double theta;
+    int p_max;
+    int* cnt;
+    const int* prp;
+    int* pcol;
+    double* pval;
+    unsigned char* ovf;  // per row: runs the scratch path
+    int* ovf_list;       // rows flagged by the count pass, ovf_n[0] of them
+    int* ovf_n;
+    int* err;            // a scratch table filled up (cannot happen: sized from the row's bound)
+    int row0;            // first row of this launch (launches are chunked: kExtLaunchRows)
+};
+
+// an overflow row's tables in global scratch: T hash slots (a power of two), T / 2 list members
+struct ExtSlot {
+    long long io, dof, bo;  // offsets into the int / double / byte scratch
+    int row, T, slen;
+};
+
+// Orders one wave's table writes before its other lanes' reads.  The tables are private to the
+// wave.  In LDS nothing more is needed.  In the scratch form (global memory) the plain stores
+// and loads of raw / lst / sk / fl / w rely on a wave's own stores being visible to its later
+// loads through the CU's vector L1 (write-through, one L1 per CU: the default, non-split
+// mode), so a wavefront-scope fence is enough; only the hash set, which is written with
+// atomics that go to L2, is read back with an agent-scope atomic load.
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+// 1: g claimed an empty slot, 0: already there, -1: no slot left after T probes.
+// T is a power of two >= 128: the home slot is the top log2(T) bits of the product
+__device__ __forceinline__ int ext_insert(int* tab, int T, int g) {
+    unsigned h = ((unsigned)g * 0x9E3779B1u) >> (__clz(T) + 1);
+    for (int p = 0; p < T; ++p) {
+        const int old = atomicCAS(&tab[h], -1, g);
+        if (old == -1) return 1;
+        if (old == g) return 0;
+        h = (h + 1) & (unsigned)(T - 1);
+    }
+    return -1;
+}
+
+// One F row.  tab[T] (all -1 on entry), raw[cap], lst[cap], sk[scap], w[cap], fl[max(cap, scap)];
+// w may alias tab (the set is dead once compacted).  Returns false if the row does not fit
+// (nothing written); GLOBAL: the tables are global memory (the set is read back past the L1).
+template <bool FILL, bool GLOBAL>
+__device__ bool ext_row(const ExtArgs& a, int i, int lane, int* tab, int T, int* raw, int* lst, int cap, double* sk,
+                        int scap, double* w, unsigned char* fl) {
+    const DCsr& A = a.R.A;
+    const DCsr& S = a.S;
+    const int gi = A.lo + i;
+    const int sb = S.rp[i], slen = S.rp[i + 1] - sb;
+    if (slen > scap) return false;
+    // a candidate is a column of a local or a ghost row: local or in D2's halo (else: err)
+    auto is_c = [&](int g) {
+        const int l = a.D2.loc(g);
+        if (l == INT_MIN) {
+            atomicExch(a.err, 1);
+            return false;
+        }
+        return (l >= 0 ? a.cf[l] : a.hcf[-l - 1]) == ST_C;
+    };
+    int m = 0;
+    bool full = false;
+    // one batch of candidates, a lane each (called by the whole wave)
+    auto batch = [&](bool valid, int g) {
+        int r = 0;
+        if (valid && is_c(g)) r = ext_insert(tab, T, g);
+        m += __popcll(__ballot(r == 1));
+        if (__ballot(r < 0)) full = true;
+    };
+    for (int t0 = 0; t0 < slen; t0 += 64) {
+        const int t = t0 + lane;
+        batch(t < slen, t < slen ? S.col[sb + t] : 0);
+        if (m > cap || full) return false;
+    }
+    for (int t = 0; t < slen; ++t) {
+        const int k = S.col[sb + t];  // wave-uniform
+        if (is_c(k)) continue;
+        const int l = a.R.D.loc(k);
+        if (l >= 0) {
+            const int b = S.rp[l], e = S.rp[l + 1];
+            for (int u0 = b; u0 < e; u0 += 64) {
+                const int u = u0 + lane;
+                batch(u < e, u < e ? S.col[u] : 0);
+                if (m > cap || full) return false;
+            }
+        } else {
+            // ghost row: strength_classical's test, the maximum over the lanes (exact)
+            const int tt = -l - 1, b = a.R.grp[tt], e = a.R.grp[tt + 1];
+            double mx = 0.0;
+            bool any = false;
+            for (int u = b + lane; u < e; u += 64) {
+                if (a.R.gcol[u] == k) continue;
+                const double v = -a.R.gval[u];
+                if (!any || v > mx) mx = v;
+                any = true;
+            }
+            for (int off = 32; off; off >>= 1) {
+                const double omx = __shfl_xor(mx, off, 64);
+                const bool oany = __shfl_xor((int)any, off, 64) != 0;
+                if (oany && (!any || omx > mx)) mx = omx;
+                any = any || oany;
+            }
+            const bool has = any && mx > 0.0;
+            const double thr = a.theta * mx;
+            for (int u0 = b; u0 < e; u0 += 64) {
+                const int u = u0 + lane;
+                const bool ok = u < e && has && a.R.gcol[u] != k && -a.R.gval[u] >= thr;
+                batch(ok, ok ? a.R.gcol[u] : 0);
+                if (m > cap || full) return false;
+            }
+        }
+    }
+    if (!FILL) {
+        if (lane == 0) a.cnt[i] = a.p_max > 0 && m > a.p_max ? a.p_max : m;
+        return true;
+    }
+    if (m == 0) return true;
+    // the set, compacted and sorted by rank (members are distinct)
+    wave_sync();
+    int base = 0;
+    for (int t0 = 0; t0 < T; t0 += 64) {
+        const int g = GLOBAL ? __hip_atomic_load(&tab[t0 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                             : tab[t0 + lane];
+        const unsigned long long mask = __ballot(g != -1);
+        if (g != -1) raw[base + __popcll(mask & ((1ull << lane) - 1ull))] = g;
+        base += __popcll(mask);
+    }
+    wave_sync();
+    for (int q = lane; q < m; q += 64) {
+        const int g = raw[q];
+        int r = 0;
+        for (int x = 0; x < m; ++x) r += raw[x] < g;
+        lst[r] = g;
+    }
+    wave_sync();
+    // s_k of the strong F neighbours, one per lane; row k's order
+    for (int t = lane; t < slen; t += 64) {
+        const int k = S.col[sb + t];
+        unsigned char f = 0;
+        double s = 0.0;
+        if (!is_c(k)) {
+            int b, e;
+            const int* rc;
+            const double* rv;
+            a.R.row(k, b, e, rc, rv);
+            double akk = 0.0;
+            for (int u = b; u < e; ++u)
+                if (rc[u] == k) {
+                    akk = rv[u];
+                    break;
+                }
+            const bool pos = akk > 0.0;
+            for (int u = b; u < e; ++u) {
+                const double v = rv[u];
+                if ((pos ? v < 0.0 : v > 0.0) && (rc[u] == gi || dfind(lst, 0, m, rc[u]) >= 0)) s += v;
+            }
+            f = EX_F | (pos ? EX_POS : 0);
+        }
+        sk[t] = s;
+        fl[t] = f;
+    }
+    wave_sync();
+    // d on lane 0, the host's order
+    const int b0 = A.rp[i], e0 = A.rp[i + 1];
+    double d = 0.0;
+    if (lane == 0) {
+        for (int k = b0; k < e0; ++k)
+            if (A.col[k] == gi) {
+                d = A.val[k];
+                break;
+            }
+        for (int k = b0; k < e0; ++k) {
+            const int j = A.col[k];
+            if (j == gi || dfind(lst, 0, m, j) >= 0 || strong(S, i, j)) continue;
+            d += A.val[k];
+        }
+        for (int t = 0; t < slen; ++t) {
+            const unsigned char f = fl[t];
+            if (!(f & EX_F)) continue;
+            const double aik = S.val[sb + t];
+            if (sk[t] == 0.0) {
+                d += aik;
+                continue;
+            }
+            int b, e;
+            const int* rc;
+            const double* rv;
+            a.R.row(S.col[sb + t], b, e, rc, rv);
+            const int u = dfind(rc, b, e, gi);
+            if (u >= 0 && ((f & EX_POS) ? rv[u] < 0.0 : rv[u] > 0.0)) d += (aik * rv[u]) / sk[t];
+        }
+    }
+    d = __shfl(d, 0, 64);
+    // w_j, one member of C^_i per lane
+    const bool trunc = a.p_max > 0 && m > a.p_max;
+    const int q0 = a.prp[i];
+    for (int q = lane; q < m; q += 64) {
+        const int j = lst[q];
+        double num = 0.0;
+        const int uij = dfind(A.col, b0, e0, j);
+        if (uij >= 0) num += A.val[uij];
+        for (int t = 0; t < slen; ++t) {
+            const unsigned char f = fl[t];
+            if (!(f & EX_F)) continue;
+            const double s = sk[t];
+            if (s == 0.0) continue;
+            int b, e;
+            const int* rc;
+            const double* rv;
+            a.R.row(S.col[sb + t], b, e, rc, rv);
+            const int u = dfind(rc, b, e, j);
+            if (u >= 0 && ((f & EX_POS) ? rv[u] < 0.0 : rv[u] > 0.0)) num += (S.val[sb + t] * rv[u]) / s;
+        }
+        const double wq = -num / d;
+        if (trunc) {
+            w[q] = wq;
+        } else {
+            a.pcol[q0 + q] = a.D2.get(a.cmap, a.hcmap, j);
+            a.pval[q0 + q] = wq;
+        }
+    }
+    if (!trunc) return true;
+    wave_sync();
+    // P_max truncation: the host's loops (sums from 0.0 in ascending column order; the larger
+    // |w| wins, ties to the smaller column); fl now marks the kept members
+    if (lane == 0) {
+        double tot = 0.0, kept = 0.0;
+        for (int q = 0; q < m; ++q) tot += w[q], fl[q] = 0;
+        for (int r = 0; r < a.p_max; ++r) {
+            int best = -1;
+            for (int q = 0; q < m; ++q)
+                if (!fl[q] && (best < 0 || fabs(w[q]) > fabs(w[best]))) best = q;
+            fl[best] = 1;
+        }
+        for (int q = 0; q < m; ++q)
+            if (fl[q]) kept += w[q];
+        const double f = kept != 0.0 ? tot / kept : 0.0;
+        int o = q0;
+        for (int q = 0; q < m; ++q) {
+            if (!fl[q]) continue;
+            a.pcol[o] = a.D2.get(a.cmap, a.hcmap, lst[q]);
+            a.pval[o++] = kept != 0.0 ? w[q] * f : w[q];
+        }
+    }
+    return true;
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(64 * kExtWaves) void interp_ext_kernel(ExtArgs a) {
+    __shared__ double wt_s[kExtWaves][kExtCap];  // the hash set (kExtTab ints), then the weights
+    __shared__ int raw_s[kExtWaves][kExtCap], lst_s[kExtWaves][kExtCap];
+    __shared__ double sk_s[kExtWaves][kExtCap];
+    __shared__ unsigned char fl_s[kExtWaves][kExtCap];
+    static_assert(kExtTab * sizeof(int) == kExtCap * sizeof(double), "the weights reuse the set's storage");
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int i = a.row0 + blockIdx.x * kExtWaves + wv;
+    if (i >= a.R.A.n) return;  // wave-uniform
+    if (a.cf[i] == ST_C) {
+        if (lane == 0) {
+            if (FILL) {
+                a.pcol[a.prp[i]] = a.cmap[i];
+                a.pval[a.prp[i]] = 1.0;
+            } else {
+                a.cnt[i] = 1;
+            }
+        }
+        return;
+    }
+    if (FILL && a.ovf[i]) return;
+    int* tab = reinterpret_cast<int*>(wt_s[wv]);
+    for (int t = lane; t < kExtTab; t += 64) tab[t] = -1;
+    wave_sync();
+    const bool ok = ext_row<FILL, false>(a, i, lane, tab, kExtTab, raw_s[wv], lst_s[wv], kExtCap, sk_s[wv], kExtCap,
+                                         wt_s[wv], fl_s[wv]);
+    if (!FILL && !ok && lane == 0) {
+        a.ovf[i] = 1;
+        a.cnt[i] = 0;
+        a.ovf_list[atomicAdd(a.ovf_n, 1)] = i;
+    }
+}
+
+// the rows the LDS form listed, a wave each, tables in global scratch (iscr preset to -1)
+template <bool FILL>
+__global__ __launch_bounds__(64 * kExtWaves) void interp_ext_scratch_kernel(ExtArgs a, const ExtSlot* slots, int nslots,
+                                                                            int* iscr, double* dscr,
+                                                                            unsigned char* bscr) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * kExtWaves + wv;
+    if (r >= nslots) return;
+    const ExtSlot sl = slots[r];
+    const int cap = sl.T / 2;
+    int* tab = iscr + sl.io;
+    const bool ok = ext_row<FILL, true>(a, sl.row, lane, tab, sl.T, tab + sl.T, tab + sl.T + cap, cap,
+                                        dscr + sl.dof + cap, sl.slen, dscr + sl.dof, bscr + sl.bo);
+    if (!ok && lane == 0) atomicExch(a.err, 1);
 }
 
 // ---- MIS(2) aggregation -----------------------------------------------------------------
@@ -1148,20 +1476,159 @@ struct DevHalo {
     }
 };
 
+// Extended+i on the device (interp_ext_kernel): init() forwards cf and the coarse ids through
+// the two-deep state halo, count() fills the row counts, fill() the entries.  Rows the LDS form
+// lists in count() run interp_ext_scratch_kernel in both passes, in batches whose scratch
+// stays under kExtScratchInts.
+constexpr int64_t kExtScratchInts = int64_t(1) << 26;  // 256 MiB of hash slots and lists per batch
+constexpr int kExtLaunchRows = 1 << 18;                // rows (wavefronts) per interp_ext_kernel launch
+static_assert(kExtLaunchRows % kExtWaves == 0, "a launch covers whole workgroups of rows");
+
+struct ExtInterp {
+    hipStream_t s = nullptr;
+    const HostCSR* A = nullptr;
+    const HaloPlan* aplan = nullptr;
+    const GhostRows* G = nullptr;
+    HaloPlan splan;
+    DevHalo SH;
+    DevBuf<int> scf, scmap, olist, on, err, iscr;
+    DevBuf<unsigned char> ovf, bscr;
+    DevBuf<double> dscr;
+    ExtArgs a{};
+    int n = 0, lo = 0, nc_global = 0;
+    int launches = 0;             // count-pass launches of the LDS form
+    std::vector<ExtSlot> slots;   // the rows of the scratch path
+
+    void init(hipStream_t stream, const HostComm& comm, const HostCSR& Ah, const HaloPlan& ap, const GhostRows& Gh,
+              const ARows& Ar, const DCsr& Sv, const int* cf, const int* cmap, int ncg, const amg_options& opt,
+              int* pcnt) {
+        s = stream, A = &Ah, aplan = &ap, G = &Gh;
+        n = Ar.A.n, lo = Ar.A.lo, nc_global = ncg;
+        if (comm.nranks > 1) splan = ext_state_plan(comm, Ah, ap, Gh);
+        SH.build(splan);
+        scf.alloc(1);
+        scmap.alloc(1);
+        if (comm.nranks > 1) {
+            SH.forward(s, comm, cf, scf);
+            SH.forward(s, comm, cmap, scmap);
+        }
+        const size_t nn = (size_t)std::max(n, 1);
+        ovf.alloc(nn);
+        olist.alloc(nn);
+        on.alloc(1);
+        err.alloc(1);
+        HIP_CHECK(hipMemsetAsync(ovf.p, 0, nn, s));
+        HIP_CHECK(hipMemsetAsync(on.p, 0, sizeof(int), s));
+        HIP_CHECK(hipMemsetAsync(err.p, 0, sizeof(int), s));
+        a.R = Ar, a.S = Sv, a.D2 = SH.dist(lo, n);
+        a.cf = cf, a.hcf = scf.p, a.cmap = cmap, a.hcmap = scmap.p;
+        a.theta = opt.strong_threshold, a.p_max = opt.p_max;
+        a.cnt = pcnt, a.prp = nullptr, a.pcol = nullptr, a.pval = nullptr;
+        a.ovf = ovf.p, a.ovf_list = olist.p, a.ovf_n = on.p, a.err = err.p;
+    }
+
+    // length of row g of A: a local row or a ghost row of A's halo
+    int64_t row_len(int64_t g) const {
+        if (g >= lo && g < lo + n) return A->rp[g - lo + 1] - A->rp[g - lo];
+        const int64_t h = aplan->find(g);
+        return G->rp[h + 1] - G->rp[h];
+    }
+
+    // the listed rows' tables: |C^_i| <= min(sum of the row lengths of row i's columns, all C)
+    void plan_slots() {
+        int no = 0;
+        HIP_CHECK(hipMemcpyAsync(&no, on.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (!no) return;
+        std::vector<int32_t> rows = download_ints(s, olist.p, no);
+        std::sort(rows.begin(), rows.end());
+        for (int32_t i : rows) {
+            int64_t ub = 0;
+            for (int64_t k = A->rp[i]; k < A->rp[i + 1]; ++k) ub += row_len(A->col[k]);
+            ub = std::min<int64_t>(std::max<int64_t>(ub, A->rp[i + 1] - A->rp[i]), std::max(nc_global, 1));
+            int64_t T = 128;
+            while (T < 2 * ub) T *= 2;
+            AMG_CHECK(T < INT_MAX, "device setup: extended+i row exceeds int32 indexing");
+            slots.push_back(ExtSlot{0, 0, 0, i, (int)T, (int)(A->rp[i + 1] - A->rp[i])});
+        }
+    }
+
+    template <bool FILL>
+    void run_slots() {
+        for (size_t c0 = 0; c0 < slots.size();) {
+            size_t c1 = c0;
+            int64_t ni = 0, nd = 0, nb = 0;
+            while (c1 < slots.size() && (c1 == c0 || ni + 2 * (int64_t)slots[c1].T <= kExtScratchInts)) {
+                ExtSlot& sl = slots[c1++];
+                sl.io = ni, sl.dof = nd, sl.bo = nb;
+                ni += 2 * (int64_t)sl.T;
+                nd += sl.T / 2 + sl.slen;
+                nb += sl.T / 2 + sl.slen;
+            }
+            if (iscr.n < (size_t)ni) iscr.alloc((size_t)ni);
+            if (dscr.n < (size_t)nd) dscr.alloc((size_t)nd);
+            if (bscr.n < (size_t)nb) bscr.alloc((size_t)nb);
+            HIP_CHECK(hipMemsetAsync(iscr.p, 0xFF, sizeof(int) * (size_t)ni, s));
+            DevBuf<ExtSlot> ds;
+            ds.upload(slots.data() + c0, c1 - c0);
+            const int ns = (int)(c1 - c0);
+            hipLaunchKernelGGL(interp_ext_scratch_kernel<FILL>, dim3((unsigned)((ns + kExtWaves - 1) / kExtWaves)),
+                               dim3(64 * kExtWaves), 0, s, a, ds.p, ns, iscr.p, dscr.p, bscr.p);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipStreamSynchronize(s));  // ds and the batch's scratch are reused
+            c0 = c1;
+        }
+    }
+
+    // a wave per row: 64 n threads pass the 2^32 threads of one grid dimension from n = 2^26 rows
+    // on (7-pt 512^3 on one rank), so the rows go in launches of kExtLaunchRows (as spgemm.hip
+    // chunks its row kernels); returns the number of launches
+    template <bool FILL>
+    int launch_rows() {
+        int launches = 0;
+        for (int64_t r0 = 0; r0 < n; r0 += kExtLaunchRows, ++launches) {
+            const int rows = (int)std::min<int64_t>(kExtLaunchRows, n - r0);
+            a.row0 = (int)r0;
+            hipLaunchKernelGGL(interp_ext_kernel<FILL>, dim3((unsigned)((rows + kExtWaves - 1) / kExtWaves)),
+                               dim3(64 * kExtWaves), 0, s, a);
+            HIP_CHECK(hipGetLastError());
+        }
+        a.row0 = 0;
+        return launches;
+    }
+
+    void count() {
+        launches = launch_rows<false>();
+        plan_slots();
+        run_slots<false>();
+    }
+
+    void fill(const int* prp, int* pcol, double* pval) {
+        a.prp = prp, a.pcol = pcol, a.pval = pval;
+        launch_rows<true>();
+        run_slots<true>();
+        int e = 0;
+        HIP_CHECK(hipMemcpyAsync(&e, err.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        AMG_ASSERT(e == 0);
+    }
+};
+
 }  // namespace
 
 // One level of the setup on the device: P and the integer split (C/F marker for RS-family
 // coarsening, aggregate id for SA), on any number of ranks.  Each rank works on its rows
 // with global column ids; the states of other ranks' points arrive through halo forwards
 // (pack on the device, the setup exchange on the host) -- exactly the synchronous rounds of
-// host_setup.cpp pmis_split / interp_classical / mis2_aggregate / sa_prolongator, so the
+// host_setup.cpp pmis_split / interp_classical / interp_ext_i / mis2_aggregate / sa_prolongator, so the
 // hierarchy is bit-identical to the host path's at every rank count.  Returns false for
 // Ruge-Stueben (the serial first pass stays on the host).
 bool level_setup_device(Context& ctx, const HostComm& comm, const HostCSR& A, const amg_options& opt,
-                        int level, HostCSR& P, std::vector<int32_t>& split, SetupImages* imgs) {
-    // Ruge-Stueben (serial first pass) and extended+i (one rank, host): the host path
+                        int level, HostCSR& P, std::vector<int32_t>& split, SetupImages* imgs, int64_t* ext_stats) {
+    if (ext_stats) ext_stats[0] = ext_stats[1] = 0;
+    // Ruge-Stueben (serial first pass): the host path
     if (opt.coarsen == AMG_COARSEN_RS) return false;
-    if (opt.coarsen == AMG_COARSEN_PMIS && opt.interp == AMG_INTERP_EXT_I) return false;
+    const bool ext = opt.coarsen == AMG_COARSEN_PMIS && opt.interp == AMG_INTERP_EXT_I;
     hipStream_t s = ctx.stream;
     const int n = (int)A.nrows();
     if (comm.nranks == 1 && n == 0) return false;
@@ -1342,13 +1809,18 @@ bool level_setup_device(Context& ctx, const HostComm& comm, const HostCSR& A, co
         DevBuf<double> pval;
         pcnt.alloc((size_t)n + 1);
         HIP_CHECK(hipMemsetAsync(pcnt.p, 0, sizeof(int) * pcnt.n, s));
+        // extended+i: the state halo two deep (cf and coarse ids), then count / scan / fill too
+        ExtInterp X;
+        if (ext) X.init(s, comm, A, aplan, G, Ar, Sv, cf.p, cmap.p, (int)cstarts[comm.nranks], opt, pcnt.p);
         // long rows (the Galerkin levels): a wave per row (interp_wave_kernel); AMG_INTERP_WAVE_NPR
         // sets the average row length from which it is taken (default 12; 0: always)
         const char* wenv = std::getenv("AMG_INTERP_WAVE_NPR");
         const int wave_npr = wenv && *wenv ? std::atoi(wenv) : 12;
         const bool wave = n > 0 && A.nnz() >= (int64_t)wave_npr * n;
         const dim3 wgrid((unsigned)((n + kIwWaves - 1) / kIwWaves)), wblk(64 * kIwWaves);
-        if (n && wave)
+        if (n && ext)
+            X.count();
+        else if (n && wave)
             hipLaunchKernelGGL(interp_wave_kernel<false>, wgrid, wblk, 0, s, Ar, Sv, cf.p, acf.p, cmap.p, acmap.p,
                                pcnt.p, nullptr, nullptr, nullptr);
         else if (n)
@@ -1358,7 +1830,9 @@ bool level_setup_device(Context& ctx, const HostComm& comm, const HostCSR& A, co
         const int64_t pnnz = exclusive_scan(s, pcnt.p, prp.p, n, tmp);
         pcol.alloc((size_t)std::max<int64_t>(pnnz, 1));
         pval.alloc((size_t)std::max<int64_t>(pnnz, 1));
-        if (n && wave)
+        if (n && ext)
+            X.fill(prp.p, pcol.p, pval.p);
+        else if (n && wave)
             hipLaunchKernelGGL(interp_wave_kernel<true>, wgrid, wblk, 0, s, Ar, Sv, cf.p, acf.p, cmap.p, acmap.p,
                                nullptr, prp.p, pcol.p, pval.p);
         else if (n)
@@ -1382,7 +1856,9 @@ bool level_setup_device(Context& ctx, const HostComm& comm, const HostCSR& A, co
             d->val = std::move(pval);
             imgs->put(P, std::move(d));
         }
-        tm.lap("  device interpolation");
+        if (ext && ext_stats) ext_stats[0] = (int64_t)X.slots.size(), ext_stats[1] = X.launches;
+        tm.lap(ext ? "  device interpolation (" + std::to_string(X.slots.size()) + " scratch rows)"
+                   : std::string("  device interpolation"));
         return true;
     }
     // smoothed aggregation (host_setup.cpp strength_symmetric, mis2_aggregate, sa_prolongator)
