@@ -366,25 +366,24 @@ int amg_par_csr_info(amg_matrix A, amg_matrix_info* info) {
         info->n_blocks = m.nb_int + m.nb_bnd;
         info->n_vi_blocks = m.n_vi_blocks;
         info->spmv_bytes = m.mode_bytes(KM_SPMV);
-        info->n_templates = m.n_tpl;
-        info->template_rows = m.tpl_on() ? m.tpl_rows : 0;
+        info->n_templates = m.tpl.n;
+        info->template_rows = m.tpl_on() ? m.tpl.rows : 0;
         info->format = m.format;
         info->kernel_variant = kernel_variant(m);
         info->csr_bytes = m.csr_plain_bytes();
         if (m.format == AMG_FORMAT_CSR) info->template_rows = 0;
         const bool tpl = m.tpl_on();
-        info->tpl_window = tpl ? m.tpl_win : 0;
-        const int w = info->tpl_window;
-        info->tpl_lanes = w <= 0 ? 0 : w <= 4 * kTPB ? 4 : w <= 8 * kTPB ? 8 : w <= 12 * kTPB ? 12 : 16;
-        info->tpl_march_shift = tpl && (info->kernel_variant & 128) ? m.tpl_march_s : 0;
+        info->tpl_window = tpl ? m.tpl.win : 0;
+        info->tpl_lanes = tpl_lanes(info->tpl_window);
+        info->tpl_march_shift = tpl && (info->kernel_variant & KV_MARCH) ? m.tpl.march_s : 0;
         info->mult_add_bytes = m.mode_bytes(KM_SPMV_ADD);
         info->residual_bytes = m.square ? m.mode_bytes(KM_RESID) : 0;
         info->jacobi_bytes = m.square ? m.mode_bytes(KM_JACOBI) : 0;
-        info->gs_bytes = m.gs_block > 0 ? m.gs_bytes : 0;
-        info->tpl_master = tpl && (info->kernel_variant & 512) ? m.tpl_mne : 0;
+        info->gs_bytes = m.gs.block > 0 ? m.gs.bytes : 0;
+        info->tpl_master = tpl && (info->kernel_variant & KV_MASTER) ? m.tpl.master.ne : 0;
         info->tile_line_bytes = m.tiled && m.format != AMG_FORMAT_CSR ? 8 * m.line_w : 0;
-        info->gs_split = m.gs_block > 0 && m.gs_split ? 1 : 0;
-        info->gs_chain_maxw = info->gs_split ? m.gs_cmaxw[0] | m.gs_cmaxw[1] << 16 : 0;
+        info->gs_split = m.gs.block > 0 && m.gs.split.on ? 1 : 0;
+        info->gs_chain_maxw = info->gs_split ? m.gs.split.cmaxw[0] | m.gs.split.cmaxw[1] << 16 : 0;
     });
 }
 

@@ -246,6 +246,126 @@ void loopback_halo(Context& c, int64_t seq, const double* x_send_buf, double* ha
                    const std::vector<int>& send_procs, const std::vector<int>& recv_procs,
                    const std::vector<int64_t>& recv_ptr, bool packed);
 
+// csr-stream / template kernel variant bits (kernels.hip kernel_variant): public values
+// (amg_matrix_info.kernel_variant, AMG_KERNEL_VARIANT)
+enum KernelVariant {
+    KV_XCD = 2,       // blocks in XCD order
+    KV_GATHER = 4,    // gather path (no x tile)
+    KV_VI = 8,        // value-indexed blocks (when any block qualifies)
+    KV_TPL = 32,      // row templates (when built)
+    KV_MARCH = 128,   // z-marching template windows
+    KV_C16 = 256,     // gather path with 16-bit column codes (DevMatrix::col16)
+    KV_MASTER = 512,  // uniform-stencil template rows (TplFormat::master)
+};
+
+// window doubles loaded per lane of the template kernels (their P parameter; 0: no window)
+inline int tpl_lanes(int win) {
+    return win <= 0 ? 0 : win <= 4 * kTPB ? 4 : win <= 8 * kTPB ? 8 : win <= 12 * kTPB ? 12 : 16;
+}
+
+// Row templates (square operators): rows whose columns are all local, written as
+// (column - row) offsets, values and 1/a_ii; rows with identical triples share a template.
+// id per row (kTplNone: the CSR block kernel handles the row); per template
+// hdr = start | len << 16 | diag entry << 24 (255: none), pd = 1/a_ii; entries off / val.
+struct TplFormat {
+    DevBuf<uint8_t> id;
+    std::vector<uint8_t> id_host;  // host copy (GS templates are derived from it)
+    DevBuf<int> hdr, off;
+    DevBuf<double> val, pd;
+    // the small table on the host (<= kTplMax templates, kTplEntries entries): what
+    // ensure_gs_blocks derives the GS templates from
+    std::vector<int> hdr_host, off_host;
+    std::vector<double> val_host;
+    int n = 0, n_ent = 0;  // templates, entries
+    int64_t rows = 0;      // rows the template kernel handles
+    // x window: bands of template offsets; per entry its window slot (ldo);
+    // win = window size in doubles, 0 = the bands do not fit (global x loads)
+    std::vector<int> blo, bbase;
+    DevBuf<int> ldo;
+    int win = 0, wend = 0;
+    // z-marching (KV_MARCH): stride in blocks between a block and the one whose window
+    // it reuses (0: no useful shift), and per window slot the source slot (-1: load)
+    int march_s = 0;
+    DevBuf<int> wsrc;
+    // uniform stencil (DESIGN.md 4.0 r3): every template's (offset, value) entries are a
+    // subsequence of the master template's (ne entries, window slots `slot`, values `val`,
+    // diagonal entry `diag`), every template holds the diagonal and every 1/a_ii is pd;
+    // mask (GsFormat::Tpl::mask): per (GS) template, bit e = has master entry e.
+    // ne = 0: not uniform.  em / ep: master index of offset -1 / +1 (-1: none)
+    struct Master {
+        int ne = 0, diag = -1, em = -1, ep = -1;
+        std::vector<int> slot;
+        std::vector<double> val;
+        double pd = 0.0;
+        DevBuf<unsigned> mask;
+        std::vector<unsigned> mask_host;
+    } master;
+    // workgroups of the template kernel over an operator of n_rows rows
+    int blocks(int64_t n_rows) const { return n > 0 ? (int)((n_rows + kTplRows - 1) / kTplRows) : 0; }
+};
+
+// l1 hybrid GS for one block size B <= 64: GS chunks = global multiples of B clipped to the
+// rank, packed whole into slabs of <= 64 rows (one wavefront each, lane = row).  Each slab's
+// rows are stored sliced-ELL, column-major (entry k of lane l at (off + k) * 64 + l; col -1 =
+// padding) so a lane's walk of its row is a coalesced stream.
+// dinv = 1 / (a_ii + sum of |a_ij| outside the chunk).
+struct GsFormat {
+    DevBuf<int4> slabs;  // {first row, rows, offset / 64, width}
+    DevBuf<int> col;
+    // the slabs on the host and their cell count (the sliced ELL is built by ensure_gs_ell, on
+    // first use for split operators)
+    std::vector<int4> slabs_host;
+    int64_t cells = 0;
+    bool ell_built = false;
+    DevBuf<double> val, dinv;
+    int n_slabs = 0;
+    int n_slabs_int = 0;  // slabs [0, n_slabs_int) touch no halo column (run before the wait)
+    int64_t block = 0;
+    int64_t bytes = 0;  // sliced-ELL bytes streamed per sweep
+    bool wide = false;  // average slab width >= kGsWide: the LDS-chain kernel variant
+    // value dictionary (the whole local operator takes <= 256 distinct values, e.g. a
+    // constant-coefficient stencil): 1-byte indices instead of val, four entries of a
+    // lane per dword -- entry k of lane l at (off + (k & ~3)) * 64 + 4 l + (k & 3) -- and
+    // the table (ndict values) staged in LDS by the kernel
+    DevBuf<uint8_t> vid;
+    DevBuf<double> vtab;
+    int ndict = 0;
+    // hybrid GS on row templates (DESIGN.md 4.2b): 512-row blocks whose rows all have a GS
+    // template = (row template, l1 diagonal) pair run tpl_gs_kernel; the sliced-ELL slabs
+    // above cover the other rows only
+    struct Tpl {
+        DevBuf<uint8_t> id;       // per row: GS template (kTplNone: ELL row)
+        DevBuf<int> hdr;          // per GS template: its row template's header
+        DevBuf<double> dl;        // per GS template: 1 / (a_ii + l1)
+        DevBuf<int> blocks;       // the 512-row blocks on the template kernel
+        DevBuf<double> cvm, cvp;  // per GS template: value of its -1 / +1 entry (or 0)
+        DevBuf<int> cf;           // per GS template: bit 0 has a -1 entry, bit 1 a +1 entry
+        DevBuf<int> kem, kep;     // per GS template: index in the row of its -1 / +1 entry (-1)
+        DevBuf<double> racc;      // per row: b - old-value couplings (acc kernel -> chain kernel)
+        DevBuf<unsigned> mask;    // per GS template: its row template's master-entry mask
+        int n = 0, n_blk = 0;
+    } tpl;
+    // split GS sweep (no GS templates): old[0 / 1] = the operator without the
+    // forward / backward sweep's in-chunk new-value couplings, in CSR-block format (its
+    // KM_GSACC pass leaves acc in `acc`); cslabs / ccol / cval[0 / 1] = the same slabs' sliced
+    // ELL holding only those couplings, in consumption order (backward: descending column) for
+    // gs_chain_kernel
+    struct Split {
+        bool on = false;
+        std::unique_ptr<DevMatrix> old[2];
+        DevBuf<int4> cslabs[2];
+        DevBuf<int> ccol[2];
+        DevBuf<double> cval[2];
+        DevBuf<double> acc;
+        int cmaxw[2] = {0, 0};  // widest chain-ELL slab per direction
+        // chain slabs ordered by width bucket (gs_chain_bucket): bucket q is slabs
+        // [cbucket[d][q], cbucket[d][q + 1]), walked by gs_chain_kernel<., kGsChainW[q]>
+        int cbucket[2][kGsChainBuckets + 1] = {};
+    } split;
+    // norm partials one forward sweep leaves
+    int norm_parts() const { return n_slabs + kNormParts * tpl.n_blk; }
+};
+
 // ParCSRMatrix on the device: rank-local rows, columns renumbered [local | halo].
 struct DevMatrix {
     Context* ctx = nullptr;
@@ -265,6 +385,9 @@ struct DevMatrix {
     // touch halo columns.  Each block is {row begin, row end}.
     DevBuf<int2> blocks;
     int nb_int = 0, nb_bnd = 0;
+    // blocks [0, nb_skip) hold only templated rows: the block kernel skips them while
+    // templates are active (tpl_on())
+    int nb_skip = 0;
     // per block 2 x int4 = {r0, r1, k0, nnz}, {diag slot, tile lines, value-table offset
     // (-1: value stream), value-table size}: everything a block needs before its bulk loads
     DevBuf<int4> hdr;
@@ -293,58 +416,12 @@ struct DevMatrix {
     DevBuf<uint8_t> vidx;
     int n_vi_blocks = 0;
     int64_t vi_nnz = 0;  // nonzeros in value-indexed blocks
-    // csr-stream variant bits (kernels.hip): 2 = XCD block order, 4 = gather (no x tile).
+    // csr-stream variant bits (KernelVariant): KV_XCD, KV_GATHER.
     // Set at build: x tile for square operators; gather + XCD order for rectangular ones.
     int default_variant = 0;
     // rows per lane of gather blocks: kGatherRPB for short-row rectangular operators (avg <= 4
     // entries per row: P of the classical hierarchy), whose blocks then hold up to 1024 rows
     int gather_rpb = 1;
-    // l1 hybrid GS (built on first use for a given block size B <= 64): GS chunks = global
-    // multiples of B clipped to this rank, packed whole into slabs of <= 64 rows (one
-    // wavefront each, lane = row).  Each slab's rows are stored sliced-ELL, column-major
-    // (entry k of lane l at (off + k) * 64 + l; col -1 = padding) so a lane's walk of its
-    // row is a coalesced stream.  gs_dinv = 1 / (a_ii + sum of |a_ij| outside the chunk).
-    DevBuf<int4> gs_slabs;  // {first row, rows, offset / 64, width}
-    DevBuf<int> gs_col;
-    // the slabs on the host and their cell count (the sliced ELL is built by ensure_gs_ell, on
-    // first use for split operators)
-    std::vector<int4> gs_slabs_host;
-    int64_t gs_cells = 0;
-    bool gs_ell_built = false;
-    void ensure_gs_ell();
-    void ensure_gs_pass(int d);  // gs_old[d], built on first use (ensure_gs_blocks: d = 1)
-    DevBuf<double> gs_val, gs_dinv;
-    int n_gs_slabs = 0;
-    int n_gs_slabs_int = 0;  // slabs [0, n_gs_slabs_int) touch no halo column (run before the wait)
-    int64_t gs_block = 0;
-    // hybrid GS on row templates (DESIGN.md 4.2b): 512-row blocks whose rows all have a GS
-    // template = (row template, l1 diagonal) pair run tpl_gs_kernel; the sliced-ELL slabs
-    // above cover the other rows only
-    DevBuf<uint8_t> gs_tid;      // per row: GS template (kTplNone: ELL row)
-    DevBuf<int> gs_thdr;         // per GS template: its row template's header
-    DevBuf<double> gs_tdl;       // per GS template: 1 / (a_ii + l1)
-    DevBuf<int> gs_tblocks;      // the 512-row blocks on the template kernel
-    DevBuf<double> gs_tcvm, gs_tcvp;  // per GS template: value of its -1 / +1 entry (or 0)
-    DevBuf<int> gs_tcf;          // per GS template: bit 0 has a -1 entry, bit 1 a +1 entry
-    DevBuf<int> gs_tkem, gs_tkep;  // per GS template: index in the row of its -1 / +1 entry (-1)
-    DevBuf<double> gs_racc;      // per row: b - old-value couplings (acc kernel -> chain kernel)
-    int n_gs_tpl = 0, n_gs_tblk = 0;
-    int gs_norm_parts() const { return n_gs_slabs + kNormParts * n_gs_tblk; }
-    int64_t gs_bytes = 0;  // sliced-ELL bytes streamed per sweep
-    bool gs_wide = false;  // average slab width >= kGsWide: the LDS-chain kernel variant
-    // value dictionary (the whole local operator takes <= 256 distinct values, e.g. a
-    // constant-coefficient stencil): 1-byte indices instead of gs_val, four entries of a
-    // lane per dword -- entry k of lane l at (off + (k & ~3)) * 64 + 4 l + (k & 3) -- and
-    // the table (gs_ndict values) staged in LDS by the kernel
-    DevBuf<uint8_t> gs_vid;
-    DevBuf<double> gs_vtab;
-    int gs_ndict = 0;
-    // split GS sweep (one rank or a replicated operator, no GS templates):
-    // gs_old[0 / 1] = this operator without the forward / backward sweep's in-chunk new-value
-    // couplings, in CSR-block format (its KM_GSACC pass leaves acc in gs_acc); gs_cslabs /
-    // gs_ccol / gs_cval[0 / 1] = the same slabs' sliced ELL holding only those couplings, in
-    // consumption order (backward: descending column) for gs_chain_kernel
-    std::unique_ptr<DevMatrix> gs_old[2];
     // r5: an operator the caller created (C-ABI constructors) keeps, on one rank, the CSR the
     // device format build uploaded (row pointers, columns, values in row order) until a solver
     // setup takes it as its level-0 image (SetupImages) instead of uploading the operator
@@ -352,46 +429,11 @@ struct DevMatrix {
     // frees it too, capi.hip release_setup_image)
     bool keep_setup_csr = false;
     std::unique_ptr<DevCsr> setup_csr;
-    DevBuf<int4> gs_cslabs[2];
-    DevBuf<int> gs_ccol[2];
-    DevBuf<double> gs_cval[2];
-    DevBuf<double> gs_acc;
-    bool gs_split = false;
-    int gs_cmaxw[2] = {0, 0};  // widest chain-ELL slab per direction
-    // chain slabs ordered by width bucket (gs_chain_bucket): bucket q is slabs
-    // [gs_cbucket[d][q], gs_cbucket[d][q + 1]), walked by gs_chain_kernel<., kGsChainW[q]>
-    int gs_cbucket[2][kGsChainBuckets + 1] = {};
-    // row templates (square operators): rows whose columns are all local, written as
-    // (column - row) offsets, values and 1/a_ii; rows with identical triples share a template.
-    // tpl_id per row (kTplNone: the CSR block kernel handles the row); per template
-    // tpl_hdr = start | len << 16 | diag entry << 24 (255: none), tpl_pd = 1/a_ii; entries
-    // tpl_off / tpl_val.  CSR blocks [0, nb_skip) hold only templated rows: the block kernel
-    // skips them while templates are active (tpl_on()).
-    DevBuf<uint8_t> tpl_id;
-    std::vector<uint8_t> tpl_id_host;  // host copy (GS templates are derived from it)
-    DevBuf<int> tpl_hdr, tpl_off;
-    // x window: bands of template offsets; per entry its window slot (tpl_ldo);
-    // tpl_win = window size in doubles, 0 = the bands do not fit (global x loads)
-    std::vector<int> tpl_blo, tpl_bbase;
-    DevBuf<int> tpl_ldo;
-    // z-marching (variant bit 128): stride in blocks between a block and the one whose window
-    // it reuses (0: no useful shift), and per window slot the source slot (-1: load)
-    int tpl_march_s = 0;
-    DevBuf<int> tpl_wsrc;
-    int tpl_win = 0, tpl_wend = 0;
-    DevBuf<double> tpl_val, tpl_pd;
-    int n_tpl = 0, n_tpl_ent = 0, nb_skip = 0;
-    int64_t tpl_rows = 0;  // rows the template kernel handles
-    // uniform stencil (DESIGN.md 4.0 r3): every template's (offset, value) entries are a
-    // subsequence of the master template's (tpl_mne entries, window slots tpl_mslot, values
-    // tpl_mval, diagonal entry tpl_mdiag), every template holds the diagonal and every 1/a_ii
-    // is tpl_mpd; tpl_mmask / gs_tmask: per (GS) template, bit e = has master entry e.
-    // tpl_mne = 0: not uniform.  tpl_mem / tpl_mep: master index of offset -1 / +1 (-1: none)
-    int tpl_mne = 0, tpl_mdiag = -1, tpl_mem = -1, tpl_mep = -1;
-    std::vector<int> tpl_mslot;
-    std::vector<double> tpl_mval;
-    double tpl_mpd = 0.0;
-    DevBuf<unsigned> tpl_mmask, gs_tmask;
+    TplFormat tpl;  // row templates and their x window (square operators)
+    // l1 hybrid GS, built on first use for a given block size (ensure_gs_blocks)
+    GsFormat gs;
+    void ensure_gs_ell();
+    void ensure_gs_pass(int d);  // gs.split.old[d], built on first use (ensure_gs_blocks: d = 1)
     int64_t csr_fmt_bytes = 0;  // spmv_fmt_bytes with templates off (AMG_KERNEL_VARIANT)
     // storage format the level kernels use (AMG_FORMAT_*, amg_par_csr_set_format):
     // AUTO = templates + CSR blocks (default), BLOCKS = CSR blocks only, CSR = plain CSR
@@ -419,11 +461,10 @@ struct DevMatrix {
     int64_t jac_extra_all = 0, jac_extra_csr = 0;  // Jacobi operand bytes of the CSR-kernel rows
     static int64_t format_generation;  // bumped by every set_format: captured graphs go stale
     bool tpl_on() const;
-    int tpl_blocks() const { return n_tpl > 0 ? (int)((n_rows + kTplRows - 1) / kTplRows) : 0; }
     // norm partials one NORM-mode application leaves (and the most either path can leave)
     int norm_parts() const;
     int norm_parts_max() const {
-        return std::max(nb_int + nb_bnd + tpl_blocks(), plain_blocks()) * kNormParts;
+        return std::max(nb_int + nb_bnd + tpl.blocks(n_rows), plain_blocks()) * kNormParts;
     }
     // halo (ParComm): RCCL neighbour exchange
     HaloPlan plan;
@@ -455,23 +496,23 @@ struct DevMatrix {
 enum KernelMode { KM_SPMV = 0, KM_SPMV_ADD = 1, KM_RESID = 2, KM_JACOBI = 3, KM_GSACC = 4 };
 
 // launchers (kernels.hip); all enqueue on s
-// csr-stream variant bits in effect for A (DevMatrix::default_variant, VI and template bits,
-// or AMG_KERNEL_VARIANT): 2 XCD order, 4 gather, 8 value-indexed, 32 row templates
+// KernelVariant bits in effect for A (DevMatrix::default_variant and the bits of what was
+// built -- value index, templates, march, column codes, master -- or AMG_KERNEL_VARIANT)
 int kernel_variant(const DevMatrix& A);
 // partial slot of block bid's wave w: part_off + bid * kNormParts + w
 void launch_csr_stream(hipStream_t s, int mode, bool norm, const DevMatrix& A, int first_block,
                        int n_blocks, const double* x, const double* b, double* y, double omega,
                        double* partial, int part_off = 0,
                        double* y2 = nullptr, const double* d2 = nullptr);
-// template rows of A (all of them, one launch); partials at [0, tpl_blocks() * kNormParts)
+// template rows of A (all of them, one launch); partials at [0, tpl.blocks(n_rows) * kNormParts)
 void launch_tpl(hipStream_t s, int mode, bool norm, const DevMatrix& A, const double* x,
                 const double* b, double* y, double omega, double* partial);
 // hybrid GS sweep over slabs [s0, s1) of the sliced-ELL copy, plus (tpl) the template blocks;
-// partials: slab q at q, template block list entry t, wave w at n_gs_slabs + 4 t + w
+// partials: slab q at q, template block list entry t, wave w at gs.n_slabs + 4 t + w
 void launch_hybrid_gs(hipStream_t s, const DevMatrix& A, const double* x, const double* b,
                       double* y, bool backward, double* partial, int s0, int s1, bool tpl);
 // chain walk of a split GS sweep: every slab, acc (from the KM_GSACC pass of
-// A.gs_old) minus the in-chunk new-value couplings in sweep order, y = x + acc * dinv_l1
+// A.gs.split.old) minus the in-chunk new-value couplings in sweep order, y = x + acc * dinv_l1
 void launch_gs_chain(hipStream_t s, const DevMatrix& A, const double* x, const double* acc,
                      double* y, bool backward);
 // plain CSR (AMG_FORMAT_CSR): all rows, one launch; partials at [0, plain_blocks() * kNormParts)

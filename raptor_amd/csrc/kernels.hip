@@ -712,7 +712,7 @@ __global__ __launch_bounds__(kTPB) void read_kernel(long long npair, const v2d_t
 // every workgroup reads: x[r0 + lo, r0 + kTplRows + hi] per band.  The workgroup loads the
 // bands into LDS once (NPL 8-byte loads per lane, all issued before the first is used; 512
 // contiguous bytes per wave-instruction) and every product reads x from LDS through the
-// entry's window slot (tpl_ldo).  Without the window (operators whose bands do not fit) each
+// entry's window slot (TplFormat::ldo).  Without the window (operators whose bands do not fit) each
 // product loads x from global memory, 8 entries per batch.  Measured on the 7-pt 256^3
 // operator: window 5x fewer vector-memory instructions than the global loads, which were
 // latency-bound at ~1/4 of the HBM rate (profiles/r1t_*).
@@ -1044,7 +1044,7 @@ __device__ __forceinline__ double tpl_rows(const TplArgs& a, const TplLds& L, __
 }
 
 // Uniform-stencil rows (variant bit 512): every template is the master
-// template with entries removed (DevMatrix::tpl_mne), so a row is an entry mask.  The master's
+// template with entries removed (TplFormat::master), so a row is an entry mask.  The master's
 // values and window slots are kernel arguments (scalar registers, wave-uniform), and a lane
 // reads only x from the window: per entry one LDS read, one address add, one multiply and one
 // add, where tpl_rows reads slots and values from LDS tables and selects per entry (~10 VALU
@@ -2042,9 +2042,9 @@ void launch_append(hipStream_t s, const double* v, double* hist, int* counter) {
 }
 
 int kernel_variant(const DevMatrix& A) {
-    // variant bits: 2 = XCD-ordered blocks, 4 = gather path (no x tile), 8 = value-indexed
-    // blocks (when any block qualifies), 32 = row templates (when built), 128 = z-marching
-    // template windows (default when a
+    // variant bits (KernelVariant, device.hpp): KV_XCD = XCD-ordered blocks, KV_GATHER =
+    // gather path (no x tile), KV_VI = value-indexed blocks (when any block qualifies), KV_TPL
+    // = row templates (when built), KV_MARCH = z-marching template windows (default when a
     // shift with enough reuse exists and the window is <= 2048 doubles: 7-pt level 0 74.5 vs
     // 80.6 us, profiles/r1u_march_ab.txt; the 27-pt window of 3078 doubles ran 204 vs 154 us,
     // profiles/r1u_sa27_kernel_stats.csv against r1t).  Default
@@ -2053,34 +2053,34 @@ int kernel_variant(const DevMatrix& A) {
     // where built.  AMG_KERNEL_VARIANT overrides the bits (experiments,
     // scripts/spmv_variants.py; results are identical).
     const char* ev = getenv("AMG_KERNEL_VARIANT");
-    int var = ev ? atoi(ev) : (A.default_variant | (A.n_vi_blocks > 0 ? 8 : 0) | (A.n_tpl > 0 ? 32 : 0) |
-                                (A.tpl_march_s > 0 && A.tpl_win <= 8 * kTPB ? 128 : 0));
-    if (A.n_vi_blocks == 0) var &= ~8;
-    if (A.n_tpl == 0) var &= ~32;
+    int var = ev ? atoi(ev) : (A.default_variant | (A.n_vi_blocks > 0 ? KV_VI : 0) | (A.tpl.n > 0 ? KV_TPL : 0) |
+                                (A.tpl.march_s > 0 && A.tpl.win <= 8 * kTPB ? KV_MARCH : 0));
+    if (A.n_vi_blocks == 0) var &= ~KV_VI;
+    if (A.tpl.n == 0) var &= ~KV_TPL;
     // AMG_FORMAT_BLOCKS: the CSR block kernel on every row (no templates)
-    if (A.format == AMG_FORMAT_BLOCKS) var &= ~(32 | 128);
+    if (A.format == AMG_FORMAT_BLOCKS) var &= ~(KV_TPL | KV_MARCH);
     // each operator is stored for one kernel: square -> x tile, rectangular -> gather
-    if (A.tiled) var &= ~4;
-    else var |= 4;
-    // 256: gather path with 16-bit column codes, where built (DevMatrix::col16; default on,
+    if (A.tiled) var &= ~KV_GATHER;
+    else var |= KV_GATHER;
+    // KV_C16: gather path with 16-bit column codes, where built (DevMatrix::col16; default on,
     // AMG_GATHER_C16=0 turns it off for A/B runs)
     if (!ev && !A.tiled && A.col16.p) {
         const char* e = std::getenv("AMG_GATHER_C16");
-        if (!(e && std::atoi(e) == 0)) var |= 256;
+        if (!(e && std::atoi(e) == 0)) var |= KV_C16;
     }
-    if (!A.col16.p) var &= ~256;
-    // 512: uniform-stencil template rows, default where the templates are
-    // one master's subsequences (DevMatrix::tpl_mne; AMG_TPL_MASTER=0 at build turns it off)
-    if (!ev && A.tpl_mne > 0) var |= 512;
-    if (A.tpl_mne == 0) var &= ~512;
+    if (!A.col16.p) var &= ~KV_C16;
+    // KV_MASTER: uniform-stencil template rows, default where the templates
+    // are one master's subsequences (TplFormat::master; AMG_TPL_MASTER=0 at build turns it off)
+    if (!ev && A.tpl.master.ne > 0) var |= KV_MASTER;
+    if (A.tpl.master.ne == 0) var &= ~KV_MASTER;
     return var;
 }
 
-bool DevMatrix::tpl_on() const { return n_tpl > 0 && (kernel_variant(*this) & 32); }
+bool DevMatrix::tpl_on() const { return tpl.n > 0 && (kernel_variant(*this) & KV_TPL); }
 
 int DevMatrix::norm_parts() const {
     if (format == AMG_FORMAT_CSR) return plain_blocks() * kNormParts;
-    return tpl_on() ? (tpl_blocks() + nb_int + nb_bnd - nb_skip) * kNormParts
+    return tpl_on() ? (tpl.blocks(n_rows) + nb_int + nb_bnd - nb_skip) * kNormParts
                     : (nb_int + nb_bnd) * kNormParts;
 }
 
@@ -2145,51 +2145,59 @@ static void launch_tpl_march(hipStream_t s, const TplArgs& a, int g, size_t lds,
     }
 }
 
-void launch_tpl(hipStream_t s, int mode, bool norm, const DevMatrix& A, const double* x,
-                const double* b, double* y, double omega, double* partial) {
-    const int g = A.tpl_blocks();
-    if (g <= 0) return;
-    AMG_ASSERT(A.square && A.n_tpl > 0 && A.n_tpl <= kTplMax && A.n_tpl_ent <= kTplEntries);
-    const bool win = A.tpl_win > 0;
-    TplArgs a{};
-    a.id = A.tpl_id.p;
-    a.hdr = A.tpl_hdr.p;
-    a.off = win ? A.tpl_ldo.p : A.tpl_off.p;
-    a.val = A.tpl_val.p;
-    a.pd = A.tpl_pd.p;
-    a.ntpl = A.n_tpl;
-    a.nent = A.n_tpl_ent;
-    a.n = (int)A.n_rows;
-    a.nband = win ? (int)A.tpl_blo.size() : 0;
-    a.win = win ? A.tpl_win : 0;
-    a.wend = win ? A.tpl_wend : 0;
-    for (int q = 0; q < a.nband; ++q) a.blo[q] = A.tpl_blo[q], a.bbase[q] = A.tpl_bbase[q];
+// The part of a template launch's arguments that the row-template and the GS-template kernels
+// share: the x window and its bands (win: the window is in use) and, for a uniform stencil
+// (mne > 0, KV_MASTER), the master's entries -- hdr = `mask`, the per-template entry masks
+// (the row templates' or the GS templates'), instead of the template tables
+static void tpl_window_args(TplArgs& a, const TplFormat& T, bool win, int mne, const DevBuf<unsigned>& mask) {
+    a.nband = win ? (int)T.blo.size() : 0;
+    a.win = win ? T.win : 0;
+    a.wend = win ? T.wend : 0;
+    for (int q = 0; q < a.nband; ++q) a.blo[q] = T.blo[q], a.bbase[q] = T.bbase[q];
     a.bbase[a.nband] = a.win;
     for (int q = a.nband; q < kTplBands; ++q) a.blo[q] = 0, a.bbase[q + 1] = a.win;
     tpl_chunk_tables(a);
+    if (mne > 0) {
+        AMG_ASSERT(mne <= kTplMasterMax && (int)T.master.slot.size() == mne && mask.n >= (size_t)a.ntpl);
+        a.hdr = (const int*)mask.p;
+        a.nent = 0;
+        a.mdiag = T.master.diag;
+        a.mpd = T.master.pd;
+        for (int e = 0; e < mne; ++e) a.mslot[e] = T.master.slot[e], a.mval[e] = T.master.val[e];
+    }
+}
+
+void launch_tpl(hipStream_t s, int mode, bool norm, const DevMatrix& A, const double* x,
+                const double* b, double* y, double omega, double* partial) {
+    const int g = A.tpl.blocks(A.n_rows);
+    if (g <= 0) return;
+    AMG_ASSERT(A.square && A.tpl.n > 0 && A.tpl.n <= kTplMax && A.tpl.n_ent <= kTplEntries);
+    const bool win = A.tpl.win > 0;
+    TplArgs a{};
+    a.id = A.tpl.id.p;
+    a.hdr = A.tpl.hdr.p;
+    a.off = win ? A.tpl.ldo.p : A.tpl.off.p;
+    a.val = A.tpl.val.p;
+    a.pd = A.tpl.pd.p;
+    a.ntpl = A.tpl.n;
+    a.nent = A.tpl.n_ent;
+    a.n = (int)A.n_rows;
     a.x = x;
     a.b = b;
     a.y = y;
     a.omega = omega;
     a.partial = partial;
-    // uniform stencil (variant bit 512): entry masks instead of the template tables
-    const int mne = win && (kernel_variant(A) & 512) ? A.tpl_mne : 0;
-    if (mne > 0) {
-        AMG_ASSERT(mne <= kTplMasterMax && (int)A.tpl_mslot.size() == mne && A.tpl_mmask.n >= (size_t)A.n_tpl);
-        a.hdr = (const int*)A.tpl_mmask.p;
-        a.nent = 0;
-        a.mdiag = A.tpl_mdiag;
-        a.mpd = A.tpl_mpd;
-        for (int e = 0; e < mne; ++e) a.mslot[e] = A.tpl_mslot[e], a.mval[e] = A.tpl_mval[e];
-    }
-    const int npl = !win ? 0 : a.win <= 4 * kTPB ? 4 : a.win <= 8 * kTPB ? 8 : a.win <= 12 * kTPB ? 12 : 16;
+    // uniform stencil (KV_MASTER): entry masks instead of the template tables
+    const int mne = win && (kernel_variant(A) & KV_MASTER) ? A.tpl.master.ne : 0;
+    tpl_window_args(a, A.tpl, win, mne, A.tpl.master.mask);
+    const int npl = tpl_lanes(a.win);
     AMG_ASSERT(a.win <= npl * kTPB && a.win <= kTplWin);
     const size_t lds = tpl_lds_bytes(a.win, a.nent, mode == KM_JACOBI);
-    const bool march = win && A.tpl_march_s > 0 && (kernel_variant(A) & 128);
-    if (march) a.wsrc = A.tpl_wsrc.p;
+    const bool march = win && A.tpl.march_s > 0 && (kernel_variant(A) & KV_MARCH);
+    if (march) a.wsrc = A.tpl.wsrc.p;
 #define AMG_T3(M, N, P, K)                                                     \
     do {                                                                       \
-        if (march) launch_tpl_march<M, N, P, K>(s, a, g, lds, A.tpl_march_s);  \
+        if (march) launch_tpl_march<M, N, P, K>(s, a, g, lds, A.tpl.march_s);  \
         else launch_tpl_window<M, N, P, K>(s, a, g, lds);                      \
     } while (0)
 #define AMG_T2(M, N, P)                       \
@@ -2267,12 +2275,12 @@ void launch_csr_stream(hipStream_t s, int mode, bool norm, const DevMatrix& A, i
               b, y2 ? d2 : A.dinv.p, y, omega, partial, part_off, y2, nullptr, A.gband.p, n_blocks};
     const dim3 g(n_blocks);
     const int var = kernel_variant(A);
-    if (var & 256) a.col16 = A.col16.p;
+    if (var & KV_C16) a.col16 = A.col16.p;
     const bool rpb4 = A.gather_rpb > 1;
 #define AMG_L1(M, N, X, T, V) launch_block<M, N, X, T, V>(s, g, a, first_block, rpb4, A.line_w)
 #define AMG_L2(M, N, V)                                               \
     do {                                                              \
-        const bool xo = var & 2, tl = !(var & 4);                     \
+        const bool xo = var & KV_XCD, tl = !(var & KV_GATHER);        \
         if (xo && tl) AMG_L1(M, N, true, true, V);                    \
         else if (xo) AMG_L1(M, N, true, false, V);                    \
         else if (tl) AMG_L1(M, N, false, true, V);                    \
@@ -2280,7 +2288,7 @@ void launch_csr_stream(hipStream_t s, int mode, bool norm, const DevMatrix& A, i
     } while (0)
 #define AMG_L(M, N)                                                   \
     do {                                                              \
-        if (var & 8) AMG_L2(M, N, true);                              \
+        if (var & KV_VI) AMG_L2(M, N, true);                          \
         else AMG_L2(M, N, false);                                     \
     } while (0)
 #if AMG_CSR_PHASES
@@ -2394,54 +2402,41 @@ inline size_t tpl_gs_lds_bytes(int win, int nent, int ntpl) {
 
 static void launch_tpl_gs(hipStream_t s, const DevMatrix& A, const double* x, const double* b,
                           double* y, bool backward, double* partial) {
-    AMG_ASSERT(A.n_gs_tblk > 0 && A.tpl_win > 0 && A.n_tpl_ent <= kTplEntries);
-    AMG_ASSERT(A.gs_racc.n >= (size_t)A.n_rows);
+    AMG_ASSERT(A.gs.tpl.n_blk > 0 && A.tpl.win > 0 && A.tpl.n_ent <= kTplEntries);
+    AMG_ASSERT(A.gs.tpl.racc.n >= (size_t)A.n_rows);
     TplGsArgs g{};
     TplArgs& a = g.t;
-    a.id = A.gs_tid.p;
-    a.hdr = A.gs_thdr.p;
-    a.off = A.tpl_ldo.p;
-    a.val = A.tpl_val.p;
-    a.pd = A.gs_tdl.p;
-    a.ntpl = A.n_gs_tpl;
-    a.nent = A.n_tpl_ent;
+    a.id = A.gs.tpl.id.p;
+    a.hdr = A.gs.tpl.hdr.p;
+    a.off = A.tpl.ldo.p;
+    a.val = A.tpl.val.p;
+    a.pd = A.gs.tpl.dl.p;
+    a.ntpl = A.gs.tpl.n;
+    a.nent = A.tpl.n_ent;
     a.n = (int)A.n_rows;
-    a.nband = (int)A.tpl_blo.size();
-    a.win = A.tpl_win;
-    a.wend = A.tpl_wend;
-    for (int q = 0; q < a.nband; ++q) a.blo[q] = A.tpl_blo[q], a.bbase[q] = A.tpl_bbase[q];
-    a.bbase[a.nband] = a.win;
-    for (int q = a.nband; q < kTplBands; ++q) a.blo[q] = 0, a.bbase[q + 1] = a.win;
-    tpl_chunk_tables(a);
     a.x = x;
     a.b = b;
-    a.y = A.gs_racc.p;
+    a.y = A.gs.tpl.racc.p;
     a.partial = partial;
-    g.ke = backward ? A.gs_tkep.p : A.gs_tkem.p;
+    g.ke = backward ? A.gs.tpl.kep.p : A.gs.tpl.kem.p;
     // every block on the template path (27-pt): no block list to load before the window
-    const bool all_blocks = A.n_gs_tblk == A.tpl_blocks();
-    g.blocks = all_blocks ? nullptr : A.gs_tblocks.p;
-    g.nblk = A.n_gs_tblk;
+    const bool all_blocks = A.gs.tpl.n_blk == A.tpl.blocks(A.n_rows);
+    g.blocks = all_blocks ? nullptr : A.gs.tpl.blocks.p;
+    g.nblk = A.gs.tpl.n_blk;
     g.first_row = A.first_row;
-    g.B = (int)A.gs_block;
-    g.part_off = A.n_gs_slabs;
-    // uniform stencil (variant bit 512): GS-template entry masks; the kernel's chain entry is
+    g.B = (int)A.gs.block;
+    g.part_off = A.gs.n_slabs;
+    // uniform stencil (KV_MASTER): GS-template entry masks; the kernel's chain entry is
     // master entry 2 / 4 (7-pt) or 12 / 14 (27-pt): offsets -1 / +1
-    const int mne = (kernel_variant(A) & 512) && A.gs_tmask.p &&
-                            ((A.tpl_mne == 7 && A.tpl_mem == 2 && A.tpl_mep == 4) ||
-                             (A.tpl_mne == 27 && A.tpl_mem == 12 && A.tpl_mep == 14))
-                        ? A.tpl_mne
+    const int mne = (kernel_variant(A) & KV_MASTER) && A.gs.tpl.mask.p &&
+                            ((A.tpl.master.ne == 7 && A.tpl.master.em == 2 && A.tpl.master.ep == 4) ||
+                             (A.tpl.master.ne == 27 && A.tpl.master.em == 12 && A.tpl.master.ep == 14))
+                        ? A.tpl.master.ne
                         : 0;
-    if (mne > 0) {
-        a.hdr = (const int*)A.gs_tmask.p;
-        a.nent = 0;
-        a.mdiag = A.tpl_mdiag;
-        a.mpd = A.tpl_mpd;
-        for (int e = 0; e < mne; ++e) a.mslot[e] = A.tpl_mslot[e], a.mval[e] = A.tpl_mval[e];
-    }
+    tpl_window_args(a, A.tpl, true, mne, A.gs.tpl.mask);
     const bool norm = partial != nullptr;
     const dim3 grid(g.nblk), blk(kTPB);
-    const int npl = a.win <= 4 * kTPB ? 4 : a.win <= 8 * kTPB ? 8 : a.win <= 12 * kTPB ? 12 : 16;
+    const int npl = tpl_lanes(a.win);
     AMG_ASSERT(a.win <= npl * kTPB && a.win <= kTplWin);
     const size_t lds = tpl_gs_lds_bytes(a.win, a.nent, a.ntpl);
 #define AMG_G3(BK, NM, P, K) hipLaunchKernelGGL((tpl_gs_acc_kernel<BK, NM, P, K>), grid, blk, lds, s, g)
@@ -2467,10 +2462,10 @@ static void launch_tpl_gs(hipStream_t s, const DevMatrix& A, const double* x, co
 #undef AMG_G2
 #undef AMG_G3
     HIP_CHECK(hipGetLastError());
-    TplGsChainArgs c{A.gs_racc.p, x, A.gs_tid.p, A.gs_tdl.p, backward ? A.gs_tcvp.p : A.gs_tcvm.p,
-                     A.gs_tcf.p, A.n_gs_tpl, g.blocks, A.n_gs_tblk, (int)A.gs_block, (int)A.n_rows,
+    TplGsChainArgs c{A.gs.tpl.racc.p, x, A.gs.tpl.id.p, A.gs.tpl.dl.p, backward ? A.gs.tpl.cvp.p : A.gs.tpl.cvm.p,
+                     A.gs.tpl.cf.p, A.gs.tpl.n, g.blocks, A.gs.tpl.n_blk, (int)A.gs.block, (int)A.n_rows,
                      (long long)A.first_row, y};
-    const long long nch = (long long)A.n_gs_tblk * (kTplRows / A.gs_block);
+    const long long nch = (long long)A.gs.tpl.n_blk * (kTplRows / A.gs.block);
     const dim3 cg((unsigned)((nch + 63) / 64)), cb(64);
     const size_t clds = (size_t)c.ntpl * (8 + 8 + 4);
     if (backward) hipLaunchKernelGGL((tpl_gs_chain_kernel<true>), cg, cb, clds, s, c);
@@ -2481,17 +2476,17 @@ static void launch_tpl_gs(hipStream_t s, const DevMatrix& A, const double* x, co
 void launch_hybrid_gs(hipStream_t s, const DevMatrix& A, const double* x, const double* b,
                       double* y, bool backward, double* partial, int s0, int s1, bool tpl) {
     AMG_ASSERT(!(backward && partial));
-    if (tpl && A.n_gs_tblk > 0) launch_tpl_gs(s, A, x, b, y, backward, partial);
+    if (tpl && A.gs.tpl.n_blk > 0) launch_tpl_gs(s, A, x, b, y, backward, partial);
     if (s1 <= s0) return;
-    GsArgs a{A.gs_slabs.p, A.gs_col.p, A.gs_val.p, x, A.halo.p, (int)A.n_cols_local, b,
-             A.gs_dinv.p, y, (long long)A.first_row, (long long)A.gs_block, (int)A.n_rows,
-             s1, partial, A.gs_vid.p, A.gs_vtab.p, A.gs_ndict, s0};
-    const bool wide = A.gs_wide;
+    GsArgs a{A.gs.slabs.p, A.gs.col.p, A.gs.val.p, x, A.halo.p, (int)A.n_cols_local, b,
+             A.gs.dinv.p, y, (long long)A.first_row, (long long)A.gs.block, (int)A.n_rows,
+             s1, partial, A.gs.vid.p, A.gs.vtab.p, A.gs.ndict, s0};
+    const bool wide = A.gs.wide;
     const int ns = s1 - s0;
     const dim3 grid(wide ? ns : (ns + 3) / 4), block(wide ? 64 : 256);
 #define AMG_GS(BK, WD, NM)                                                                          \
     do {                                                                                            \
-        if (A.gs_ndict > 0) hipLaunchKernelGGL((hybrid_gs_kernel<BK, WD, NM, true>), grid, block, 0, s, a); \
+        if (A.gs.ndict > 0) hipLaunchKernelGGL((hybrid_gs_kernel<BK, WD, NM, true>), grid, block, 0, s, a); \
         else hipLaunchKernelGGL((hybrid_gs_kernel<BK, WD, NM, false>), grid, block, 0, s, a);      \
     } while (0)
     if (wide) {
@@ -2572,16 +2567,16 @@ __global__ __launch_bounds__(64) void gs_chain_kernel(GsArgs a) {
 void launch_gs_chain(hipStream_t s, const DevMatrix& A, const double* x, const double* acc,
                      double* y, bool backward) {
     const int d = backward ? 1 : 0;
-    const int ns = A.n_gs_slabs;
+    const int ns = A.gs.n_slabs;
     if (ns <= 0) return;
-    GsArgs a{A.gs_cslabs[d].p, A.gs_ccol[d].p, A.gs_cval[d].p, x, A.halo.p, (int)A.n_cols_local, acc,
-             A.gs_dinv.p, y, (long long)A.first_row, (long long)A.gs_block, (int)A.n_rows,
+    GsArgs a{A.gs.split.cslabs[d].p, A.gs.split.ccol[d].p, A.gs.split.cval[d].p, x, A.halo.p, (int)A.n_cols_local, acc,
+             A.gs.dinv.p, y, (long long)A.first_row, (long long)A.gs.block, (int)A.n_rows,
              ns, nullptr, nullptr, nullptr, 0, 0};
-    AMG_ASSERT(A.gs_cmaxw[d] <= 64);  // <= 63: in-chunk couplings of a <= 64-row chunk
-    AMG_ASSERT(A.gs_cbucket[d][kGsChainBuckets] == ns);
-    // one launch, at the widest slab's width bucket (DevMatrix::gs_cbucket)
+    AMG_ASSERT(A.gs.split.cmaxw[d] <= 64);  // <= 63: in-chunk couplings of a <= 64-row chunk
+    AMG_ASSERT(A.gs.split.cbucket[d][kGsChainBuckets] == ns);
+    // one launch, at the widest slab's width bucket (GsFormat::Split::cbucket)
     for (int q = 0; q < kGsChainBuckets; ++q) {
-        const int b0 = A.gs_cbucket[d][q], b1 = A.gs_cbucket[d][q + 1];
+        const int b0 = A.gs.split.cbucket[d][q], b1 = A.gs.split.cbucket[d][q + 1];
         if (b1 <= b0) continue;
         a.slab0 = b0;
         a.nslab = b1;

@@ -289,7 +289,7 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
         // cycles: its sliced ELL is built now even where the other sweeps run split
         if (l == 0) Al.ensure_gs_ell();
         // a forward split sweep on x != 0: level 0's (tol > 0 solves), a second pre-sweep
-        if (Al.gs_split && (l == 0 || opt.pre_sweeps >= 2)) Al.ensure_gs_pass(0);
+        if (Al.gs.split.on && (l == 0 || opt.pre_sweeps >= 2)) Al.ensure_gs_pass(0);
     };
     {
         RoctxRange r("setup: hierarchy (strength, split / aggregates, P, R, Galerkin)");
@@ -440,7 +440,7 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
         if (hgs) {
             gs_build(Al, (int)l);  // done on the GS worker already where the setup overlaps
             tm.lap("L" + std::to_string(l) + " GS structures");
-            max_blocks = std::max(max_blocks, (size_t)Al.gs_norm_parts());
+            max_blocks = std::max(max_blocks, (size_t)Al.gs.norm_parts());
         }
     }
     // norm plumbing: partials | reduction scratch | gathered rank sums
@@ -520,7 +520,7 @@ void Solver::smooth(size_t l, double*& x, const double* b, double*& tmp, bool x_
         // forward GS sweep that also leaves the partials of ||b - A x|| (old x)
         AMG_ASSERT(!x_zero && !post);
         par_hybrid_gs(A, x, b, tmp, opt.gs_block, false, sink.partial);
-        norm_finish(A, sink, A.gs_norm_parts());
+        norm_finish(A, sink, A.gs.norm_parts());
     } else if (with_norm) {  // Jacobi sweep that also leaves the partials of ||b - A x||
         AMG_ASSERT(opt.smoother == AMG_SMOOTH_JACOBI && !x_zero);
         par_apply(A, KM_JACOBI, x, b, tmp, opt.jacobi_omega, sink.partial);
@@ -1173,7 +1173,7 @@ int64_t Solver::stored_bytes_per_cycle(size_t l) const {
     const int64_t n = A.n_rows;
     if (l + 1 == levels.size()) return 8 * coarse_n * n + 8 * coarse_n + 8 * n;
     const bool gs = opt.smoother == AMG_SMOOTH_HYBRID_GS;
-    const int64_t sweep = gs ? A.gs_bytes : A.mode_bytes(KM_JACOBI);
+    const int64_t sweep = gs ? A.gs.bytes : A.mode_bytes(KM_JACOBI);
     int64_t b = 0;
     bool zero = l > 0;
     int64_t sweeps = 0;
@@ -1182,7 +1182,7 @@ int64_t Solver::stored_bytes_per_cycle(size_t l) const {
     const bool j0 = !gs && Rup && (int)l != rep_level && Rup->format != AMG_FORMAT_CSR &&
                     !Rup->tpl_on();
     // a split GS sweep from zero is its chain walk alone (par_hybrid_gs_from_zero)
-    const int64_t sweep0 = gs && A.gs_split ? sweep - A.gs_old[1]->mode_bytes(KM_RESID) - 8 * n : sweep;
+    const int64_t sweep0 = gs && A.gs.split.on ? sweep - A.gs.split.old[1]->mode_bytes(KM_RESID) - 8 * n : sweep;
     for (int k = 0; k < opt.pre_sweeps; ++k, ++sweeps) {
         if (zero && !gs) b += (j0 ? 16 : 24) * n;  // omega * dinv * b
         else b += (zero ? sweep0 : sweep) + (zero ? 8 * n : 0);  // (zero fill of x first)

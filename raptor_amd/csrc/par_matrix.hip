@@ -586,6 +586,38 @@ static TplBuild build_templates(const std::vector<int>& rp, const hvec<int>& col
     return T;
 }
 
+// The environment's build knobs, read once at the top of build_view and of
+// ensure_gs_blocks -- per build, not per process: tests change them between builds -- so that
+// every stage below is a function of its arguments.  The launch-time knobs
+// (AMG_KERNEL_VARIANT, AMG_GATHER_C16, AMG_TPL_MARCH_CHUNKS) are read by the launchers.
+struct BuildKnobs {
+    int64_t tpl_min_rows = 16384;  // AMG_TPL_MIN_ROWS: rows from which half-templated operators take templates
+    int rect_tile = -1;            // AMG_RECT_TILE=0 / 1: rectangular operators never / always on x tiles
+    int tile_line = 0;             // AMG_TILE_LINE=8 / 4: forces the x-tile line width (doubles)
+    bool trace_blocks = false;     // AMG_TRACE_BLOCKS: print the block statistics of every build
+    bool tpl_master = true;        // AMG_TPL_MASTER=0: no uniform-stencil master
+    bool gs_templates = true;      // AMG_GS_TEMPLATES=0: no GS templates
+    bool gs_split = true;          // AMG_GS_SPLIT=0: no split sweeps
+    int64_t gs_split_npr = 12;     // AMG_GS_SPLIT_NPR: entries per row from which sweeps split
+};
+
+static BuildKnobs read_build_knobs() {
+    BuildKnobs k;
+    auto off = [](const char* name) {
+        const char* e = std::getenv(name);
+        return e && std::atoi(e) == 0;
+    };
+    if (const char* e = std::getenv("AMG_TPL_MIN_ROWS")) k.tpl_min_rows = std::atoll(e);
+    if (const char* e = std::getenv("AMG_RECT_TILE")) k.rect_tile = std::atoi(e);
+    if (const char* e = std::getenv("AMG_TILE_LINE")) k.tile_line = std::atoi(e);
+    k.trace_blocks = std::getenv("AMG_TRACE_BLOCKS") != nullptr;
+    k.tpl_master = !off("AMG_TPL_MASTER");
+    k.gs_templates = !off("AMG_GS_TEMPLATES");
+    k.gs_split = !off("AMG_GS_SPLIT");
+    if (const char* e = std::getenv("AMG_GS_SPLIT_NPR")) k.gs_split_npr = std::atoll(e);
+    return k;
+}
+
 // Uniform stencil: a constant-coefficient stencil's boundary templates are
 // its interior template with entries removed.  When the longest template (the master) has a
 // kernel instantiation (7 or 27 entries) and every template's (offset, value bits) entries are
@@ -593,16 +625,10 @@ static TplBuild build_templates(const std::vector<int>& rp, const hvec<int>& col
 // diagonal with the same 1/a_ii, a row is (master, entry mask): the kernels take values and
 // window slots from kernel arguments and skip the entries a row lacks.  The products and their
 // order are the row's own, so results are unchanged (bit-identical).
-static void find_master_template(DevMatrix& D, const TplBuild& tb, const std::vector<int>& ldo) {
-    D.tpl_mne = 0;
-    D.tpl_mdiag = D.tpl_mem = D.tpl_mep = -1;
-    D.tpl_mslot.clear();
-    D.tpl_mval.clear();
-    D.tpl_mmask.reset();
-    const char* env = std::getenv("AMG_TPL_MASTER");
-    if (env && std::atoi(env) == 0) return;
+static TplFormat::Master find_master_template(const TplBuild& tb, const std::vector<int>& ldo) {
+    TplFormat::Master m;
     const int nt = (int)tb.hdr.size();
-    if (nt == 0) return;
+    if (nt == 0) return m;
     auto start = [&](int t) { return tb.hdr[t] & 0xffff; };
     auto len = [&](int t) { return (tb.hdr[t] >> 16) & 0xff; };
     auto diag = [&](int t) { return (int)((unsigned)tb.hdr[t] >> 24); };
@@ -615,31 +641,33 @@ static void find_master_template(DevMatrix& D, const TplBuild& tb, const std::ve
     for (int t = 1; t < nt; ++t)
         if (len(t) > len(M)) M = t;
     const int ne = len(M);
-    if ((ne != 7 && ne != 27) || diag(M) == 255) return;
+    if ((ne != 7 && ne != 27) || diag(M) == 255) return m;
     const int sm = start(M);
     std::vector<unsigned> mask(nt, 0u);
     for (int t = 0; t < nt; ++t) {
-        if (diag(t) == 255 || bits(tb.pd[t]) != bits(tb.pd[M])) return;
+        if (diag(t) == 255 || bits(tb.pd[t]) != bits(tb.pd[M])) return m;
         int e = 0;
         for (int k = 0; k < len(t); ++k) {
             const int o = tb.off[start(t) + k];
             while (e < ne && tb.off[sm + e] != o) ++e;
-            if (e == ne || bits(tb.val[start(t) + k]) != bits(tb.val[sm + e])) return;
+            if (e == ne || bits(tb.val[start(t) + k]) != bits(tb.val[sm + e])) return m;
             mask[t] |= 1u << e;
             ++e;
         }
-        if (!(mask[t] >> diag(M) & 1u)) return;
+        if (!(mask[t] >> diag(M) & 1u)) return m;
     }
-    D.tpl_mne = ne;
-    D.tpl_mdiag = diag(M);
-    D.tpl_mpd = tb.pd[M];
+    m.ne = ne;
+    m.diag = diag(M);
+    m.pd = tb.pd[M];
     for (int e = 0; e < ne; ++e) {
-        D.tpl_mslot.push_back(ldo[sm + e]);
-        D.tpl_mval.push_back(tb.val[sm + e]);
-        if (tb.off[sm + e] == -1) D.tpl_mem = e;
-        if (tb.off[sm + e] == 1) D.tpl_mep = e;
+        m.slot.push_back(ldo[sm + e]);
+        m.val.push_back(tb.val[sm + e]);
+        if (tb.off[sm + e] == -1) m.em = e;
+        if (tb.off[sm + e] == 1) m.ep = e;
     }
-    D.tpl_mmask.upload(mask.data(), mask.size());
+    m.mask.upload(mask.data(), mask.size());
+    m.mask_host = std::move(mask);
+    return m;
 }
 
 void DevMatrix::build(Context* c, HostCSR&& h, bool replicated_view) {
@@ -667,46 +695,29 @@ void DevMatrix::ensure_built() {
     deferred = false;
 }
 
-// Every device format from a CSR the caller keeps (the member `host` is shadowed by the
-// argument): Solver::setup runs this on a worker thread while the hierarchy thread still
-// reads the same CSR, and moves it into `host` after both are done.
-void DevMatrix::build_view(Context* c, const HostCSR& host, bool replicated_view) {
-    ctx = c;
-    replicated = replicated_view;
-    static const HostComm serial;  // rank 0 of 1: replicated matrices have no halo
-    const HostComm& comm = replicated ? serial : ctx->host;
-    PhaseTimer tm(comm);
-    AMG_CHECK((int)host.row_starts.size() == comm.nranks + 1, "matrix row partition size");
-    AMG_CHECK((int)host.col_starts.size() == comm.nranks + 1, "matrix column partition size");
-    first_row = host.row_starts[comm.rank];
-    n_rows = host.nrows();
-    AMG_CHECK(n_rows == host.row_starts[comm.rank + 1] - first_row, "local row count mismatch");
-    first_col = host.col_starts[comm.rank];
-    n_cols_local = host.col_starts[comm.rank + 1] - first_col;
-    nnz = host.nnz();
-    AMG_CHECK(nnz < INT_MAX && n_rows < INT_MAX, "local matrix exceeds int32 indexing");
-    square = host.n_global_rows == host.n_global_cols && host.row_starts == host.col_starts;
-    plan = halo_plan_for_cols(comm, host);
-    if (send_map && !replicated)
-        for (int64_t& v : plan.send_idx) v = (*send_map)[v];
-    AMG_CHECK(n_cols_local + plan.n_halo() < INT_MAX, "too many columns for int32");
-    tm.lap("    build: halo plan");
+// ---- the stages of DevMatrix::build_view, in the order it runs them.  H is the CSR being
+// built from (the caller's: see build_view), hrp / hcol its int32 row pointers and local
+// column numbers.
 
-    std::vector<int> hrp(n_rows + 1);
+// Local column numbering [local | halo] and the boundary class of every row (1: the row
+// touches a halo column).
+static void local_columns(const HostCSR& H, const HaloPlan& plan, int64_t first_col, int64_t n_cols_local,
+                          std::vector<int>& hrp, hvec<int>& hcol, std::vector<uint8_t>& cls) {
+    const int64_t n_rows = H.nrows(), nnz = H.nnz();
+    hrp.resize(n_rows + 1);
     // every entry written below; capacity for the kPad zero entries appended after the
     // templates, so that resize does not reallocate and copy (0.4 s for a 449 M-entry operator)
-    hvec<int> hcol;
     hcol.reserve((size_t)nnz + kPad);
     hcol.resize(nnz);
-    std::vector<uint8_t> cls(n_rows, 0);
+    cls.assign(n_rows, 0);
 #pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i <= n_rows; ++i) hrp[i] = (int)host.rp[i];
+    for (int64_t i = 0; i <= n_rows; ++i) hrp[i] = (int)H.rp[i];
     const int64_t clo = first_col, chi = first_col + n_cols_local;
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < n_rows; ++i) {
         uint8_t b = 0;
-        for (int64_t k = host.rp[i]; k < host.rp[i + 1]; ++k) {
-            const int64_t g = host.col[k];
+        for (int64_t k = H.rp[i]; k < H.rp[i + 1]; ++k) {
+            const int64_t g = H.col[k];
             if (g >= clo && g < chi) {
                 hcol[k] = (int)(g - clo);
             } else {
@@ -716,421 +727,488 @@ void DevMatrix::build_view(Context* c, const HostCSR& host, bool replicated_view
         }
         cls[i] = b;
     }
+}
+
+// Row templates: square operators whose templates cover every row, or at least half of
+// the rows of a large operator (AMG_TPL_MIN_ROWS, default 16384; tests lower it).  Empty: none.
+static TplBuild select_templates(const BuildKnobs& knobs, const HostCSR& H, const std::vector<int>& hrp,
+                                 const hvec<int>& hcol, const std::vector<double>& di, int64_t n_cols_local) {
+    const int64_t n_rows = H.nrows();
+    TplBuild tb = build_templates(hrp, hcol, H.val, di, n_cols_local);
+    const bool use = tb.rows == n_rows || (n_rows >= knobs.tpl_min_rows && 2 * tb.rows >= n_rows);
+    if (!use) tb = TplBuild();
+    return tb;
+}
+
+// The cut of an operator into row blocks: x tile or gather, and the x-tile line width.
+struct CutChoice {
+    bool tiled = false;
+    int line_w = 8;
+};
+
+// The format choices (x tile or gather, 64- or 32-byte lines) read statistics of
+// the 64-byte cut; r5 takes them from every 8th of its 64 row chunks (the whole
+// operator below 65,536 rows) and cuts the operator once, at the chosen width.  Before,
+// each choice cut the whole operator again: 0.6 s of sa27's setup.
+static CutChoice choose_cut(const BuildKnobs& knobs, const std::vector<int>& hrp, const hvec<int>& hcol,
+                            const std::vector<uint8_t>& cls, const std::vector<uint8_t>* tplf, int64_t n_cols_local,
+                            int64_t n_halo, bool square, int gather_rpb) {
+    constexpr int kSample = 8;
+    const BlockBuild s8 = build_row_blocks(hrp, hcol, cls, n_cols_local, n_halo, tplf, kTPB * gather_rpb, true,
+                                           false, 8, kSample);
+    // rectangular operators take the x-tile kernel when their blocks reuse x lines: at most
+    // 0.5 tile lines per nonzero.  Same-box A/B (profiles/r2y_rtile_*, r2z_rpb_*): 7-pt R0
+    // 106 -> 79 us (0.23 lines / nnz), R1 66 -> 53 (0.34), P0 (4 rows per lane, 0.06)
+    // 97 -> 80, P1 49 -> 39; sa27 P0 299 -> 234 (0.04), P1 33 -> 26; g3sub R0 24 -> 20
+    // (0.33), P0 19 -> 15; sa27 R1 122 -> 158 at 0.70 (a 297-entry block loading 210
+    // lines) stays on the gather kernel.
+    // AMG_RECT_TILE=0 / 1: never / always (A/B runs)
+    int64_t tile_lines_total = 0, tile_full = 0, sample_nnz = 0;
+    for (size_t q = 0; q + 1 < s8.tile_ptr.size(); ++q) {
+        const int nt = s8.tile_ptr[q + 1] - s8.tile_ptr[q];
+        tile_lines_total += nt;
+        tile_full += nt >= kTileLines;
+        sample_nnz += hrp[s8.blocks[q].y] - hrp[s8.blocks[q].x];
+    }
+    CutChoice cut;
+    const int mode = knobs.rect_tile;
+    cut.tiled = square || (mode != 0 && (mode == 1 || 2 * tile_lines_total <= sample_nnz));
+    if (knobs.trace_blocks) {
+        const int64_t lines = tile_lines_total, full = tile_full;
+        std::fprintf(stderr, "[amg-blocks] %s rows %lld cols %lld nnz %lld sampled: blocks %zu lines %lld full %lld nnz %lld rpb %d\n",
+                     square ? "square" : cut.tiled ? "rect-tiled" : "rect-gather", (long long)hrp.size() - 1,
+                     (long long)n_cols_local, (long long)hrp.back(), s8.blocks.size(), (long long)lines, (long long)full,
+                     (long long)sample_nnz, gather_rpb);
+    }
+    // x-tile line width: operators whose blocks, cut at 256 lines of
+    // 64 B, run close to the cap (>= 3/4 full on average: Galerkin operators,
+    // restrictions) are cut at 512 lines of 32 B (the 7-pt 256^3 A2: 40,250 -> 25,615
+    // blocks; R0: same-box 76 -> 70 us); P-like operators (few lines per block) keep
+    // 64-byte lines and their 1 KiB of line ids per block (sa27 P0: 234 us at 64 B, 263 at
+    // 32 B), and so do square operators the 32-byte cut saves < 20 % of the blocks (the
+    // 7-pt A1: 50,573 -> 46,841 blocks ran 144 -> 149 us; A2: 40,281 -> 25,640 ran 125 ->
+    // 102 us); restrictions gain either way (R0 91 -> 88 us at -9 %, R1 61 -> 52 at -33 %).
+    // AMG_TILE_LINE=8 / 4 forces the width.
+    if (cut.tiled && !s8.blocks.empty()) {
+        const int force = knobs.tile_line;
+        const bool tryhalf = force == 4 || (force != 8 && 4 * tile_lines_total >= 3 * (int64_t)kTileLines *
+                                                                                     (int64_t)s8.blocks.size());
+        if (tryhalf) {
+            bool take = force == 4 || !square;
+            if (!take) {
+                const BlockBuild s4 = build_row_blocks(hrp, hcol, cls, n_cols_local, n_halo, tplf,
+                                                       kTPB * gather_rpb, true, false, 4, kSample);
+                take = 5 * s4.blocks.size() <= 4 * s8.blocks.size();
+            }
+            if (take) cut.line_w = 4;
+        }
+    }
+    return cut;
+}
+
+// The row templates on the device and their small table on the host.  Rows of blocks the CSR
+// kernel still runs (blocks from bb.nb_skip on) are not the template kernel's.
+static void upload_templates(TplFormat& T, TplBuild& tb, const BlockBuild& bb, int64_t n_rows) {
+    std::vector<char> keep(n_rows, 0);
+    for (int q = 0; q < bb.nb_skip; ++q)
+        for (int r = bb.blocks[q].x; r < bb.blocks[q].y; ++r) keep[r] = 1;
+    int64_t rows = 0;
+    for (int64_t i = 0; i < n_rows; ++i) {
+        if (!keep[i]) tb.id[i] = (uint8_t)kTplNone;
+        rows += tb.id[i] != kTplNone;
+    }
+    T.rows = rows;
+    T.n = (int)tb.hdr.size();
+    T.n_ent = (int)tb.off.size();
+    T.id.upload(tb.id.data(), tb.id.size());
+    T.id_host = tb.id;
+    T.hdr.upload(tb.hdr.data(), tb.hdr.size());
+    T.off.upload(tb.off.data(), tb.off.size());
+    T.val.upload(tb.val.data(), tb.val.size());
+    T.pd.upload(tb.pd.data(), tb.pd.size());
+    T.hdr_host = tb.hdr;
+    T.off_host = tb.off;
+    T.val_host = tb.val;
+}
+
+// x window: distinct offsets merged into bands while a gap is shorter than a workgroup's rows
+// (a new band would load kTplRows more doubles than the gap); per entry its window slot.
+// Returns the slots (empty, and T.win = 0, when the bands do not fit the window).
+static std::vector<int> tpl_window(TplFormat& T, const TplBuild& tb) {
+    std::vector<int> offs(tb.off);
+    std::sort(offs.begin(), offs.end());
+    offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
+    std::vector<int2> bands;  // {lo, hi}
+    for (int o : offs) {
+        if (!bands.empty() && (int64_t)o - bands.back().y < kTplRows) bands.back().y = o;
+        else bands.push_back(make_int2(o, o));
+    }
+    // even band starts and lengths: slot pairs map to 16-byte aligned pairs of x
+    for (int2& bd : bands) bd.x &= ~1;
+    auto blen = [](const int2& bd) { return (int64_t)(kTplRows + bd.y - bd.x + 1) & ~(int64_t)1; };
+    int64_t w = 0;
+    for (const int2& bd : bands) w += blen(bd);
+    if ((int)bands.size() > kTplBands || w > kTplWin) return {};
+    std::vector<int> ldo(tb.off.size());
+    int base = 0;
+    for (const int2& bd : bands) {
+        T.blo.push_back(bd.x);
+        T.bbase.push_back(base);
+        base += (int)blen(bd);
+    }
+    T.wend = bands.back().x + (int)blen(bands.back());
+    for (size_t k = 0; k < tb.off.size(); ++k) {
+        const int o = tb.off[k];
+        size_t q = 0;
+        while (q + 1 < bands.size() && o > bands[q].y) ++q;
+        ldo[k] = T.bbase[q] + (o - bands[q].x);
+    }
+    T.win = base;
+    T.ldo.upload(ldo.data(), ldo.size());
+    return ldo;
+}
+
+// z-marching: the shift D (a multiple of kTplRows, taken from the band starts) under which
+// the most window slots of a block are slots of the block D rows back; used when at least a
+// quarter of the window is reused.  Fills T.march_s and T.wsrc from T's window.
+static void tpl_march(TplFormat& T, int64_t n_rows) {
+    const int nbd = (int)T.blo.size(), base = T.win;
+    auto reuse_map = [&](int64_t D, std::vector<int>* map) {
+        int cnt = 0;
+        for (int q = 0; q < nbd; ++q) {
+            const int len = (q + 1 < nbd ? T.bbase[q + 1] : base) - T.bbase[q];
+            for (int i = 0; i < len; ++i) {
+                const int64_t g = D + T.blo[q] + i;  // relative to the old r0
+                int src = -1;
+                for (int q2 = 0; q2 < nbd && src < 0; ++q2) {
+                    const int len2 = (q2 + 1 < nbd ? T.bbase[q2 + 1] : base) - T.bbase[q2];
+                    const int64_t j = g - T.blo[q2];
+                    if (j >= 0 && j < len2) src = T.bbase[q2] + (int)j;
+                }
+                if (map) (*map)[T.bbase[q] + i] = src;
+                cnt += src >= 0;
+            }
+        }
+        return cnt;
+    };
+    int64_t bestD = 0;
+    int best = 0;
+    std::vector<int64_t> cand;
+    for (int q = 0; q < nbd; ++q) {
+        cand.push_back(std::abs((int64_t)T.blo[q]));
+        for (int q2 = q + 1; q2 < nbd; ++q2) cand.push_back((int64_t)T.blo[q2] - T.blo[q]);
+    }
+    for (int64_t D : cand) {
+        D -= D % kTplRows;
+        if (D <= 0 || D / kTplRows > INT_MAX / 2) continue;
+        const int c = reuse_map(D, nullptr);
+        if (c > best) best = c, bestD = D;
+    }
+    // 16-byte pair loads: an even row count keeps every pair inside or outside x
+    if (bestD > 0 && 4 * best >= base && n_rows % 2 == 0) {
+        std::vector<int> map(base, -1);
+        reuse_map(bestD, &map);
+        T.march_s = (int)(bestD / kTplRows);
+        T.wsrc.upload(map.data(), map.size());
+    }
+}
+
+// The per-nonzero streams of the CSR block kernels built on the host (AMG_DEVICE_FORMATS=0;
+// formats.hip builds the same bytes on the GPU): block-aligned col / val, x-tile ids and tile
+// indices, the value index and the row ends; fi gets what the block headers need.
+static void host_block_streams(DevMatrix& M, PhaseTimer& tm, const HostCSR& H, const std::vector<int>& hrp,
+                               const hvec<int>& hcol, const BlockBuild& bb, const std::vector<int64_t>& koff,
+                               FormatHeaderInfo& fi) {
+    const size_t nbk = bb.blocks.size();
+    {
+        ParZeros<int> cb((size_t)(koff[nbk] + kPad));
+        ParZeros<double> vb(cb.size());
+#pragma omp parallel for schedule(dynamic, 256)
+        for (size_t q = 0; q < nbk; ++q) {
+            const int kb = hrp[bb.blocks[q].x], nz = hrp[bb.blocks[q].y] - kb;
+            std::copy(hcol.begin() + kb, hcol.begin() + kb + nz, cb.begin() + koff[q]);
+            std::copy(H.val.begin() + kb, H.val.begin() + kb + nz, vb.begin() + koff[q]);
+        }
+        M.col.upload(cb.data(), cb.size());
+        M.val.upload(vb.data(), vb.size());
+    }
+    if (M.tiled) {  // x tiles: the x-tile kernel only
+        // x-tile line ids at a fixed stride (kCAP / line_w per block, padded with the block's
+        // last line), so the kernel loads them without waiting for the block header
+        const int tlb = kCAP / M.line_w;
+        ParZeros<int> fx(std::max<size_t>(nbk, 1) * tlb);
+#pragma omp parallel for schedule(static)
+        for (size_t q = 0; q < nbk; ++q) {
+            const int t0 = bb.tile_ptr[q], nt = bb.tile_ptr[q + 1] - t0;
+            if (nt <= 0 || nt > tlb) continue;
+            for (int j = 0; j < tlb; ++j)
+                fx[q * tlb + j] = bb.tile_lines[t0 + std::min(j, nt - 1)];
+        }
+        M.tile_fixed.upload(fx.data(), fx.size());
+        // lane-major per block (lane_pos): lane t's 8 indices are 16 contiguous bytes,
+        // one 16-byte load per lane
+        ParZeros<uint16_t> perm(std::max<size_t>(nbk, 1) * kCAP);
+#pragma omp parallel for schedule(static)
+        for (size_t q = 0; q < nbk; ++q) {
+            const int kb = hrp[bb.blocks[q].x], nz = hrp[bb.blocks[q].y] - kb;
+            if (nz > kCAP) continue;
+            for (int j = 0; j < nz; ++j)
+                perm[q * kCAP + lane_pos(j, kCAP / kTPB)] = bb.lcol[kb + j];
+        }
+        M.lcol.upload(perm.data(), perm.size());
+    } else {
+        M.tile_fixed.reset();
+        M.lcol.reset();
+    }
+    tm.lap("    build: col / val / tile layouts");
+    std::vector<uint8_t> hdvi;
+    build_value_index(M, H, hrp, bb, fi.vt_off, fi.vt_len, hdvi, fi.dvi_ok, fi.vofs);
+    if (M.n_vi_blocks > 0 && M.square) M.dvi.upload(hdvi.data(), hdvi.size());
+    else M.dvi.reset();
+    tm.lap("    build: value index");
+    // per row: end of its nonzeros relative to its block's first (<= kCAP: 16 bits)
+    std::vector<uint16_t> re((size_t)M.n_rows + 1, 0);
+    for (size_t q = 0; q < nbk; ++q) {
+        const int2 b = bb.blocks[q];
+        if (hrp[b.y] - hrp[b.x] > kCAP) continue;
+        for (int r = b.x; r < b.y; ++r) re[r] = (uint16_t)(hrp[r + 1] - hrp[b.x]);
+    }
+    M.rend.upload(re.data(), re.size());
+}
+
+// Gather operators: 16-bit column codes when every block's columns fit in <= 4
+// bands of kGatherBand: a structured P / R block reads three
+// planes' worth of columns, each a narrow band.  Lossless: the kernel decodes
+// base[code >> 14] + (code & 0x3fff), the same column.  Left empty where a block does not fit.
+static void gather_codes(const std::vector<int>& hrp, const hvec<int>& hcol, const std::vector<int2>& blocks,
+                         const std::vector<int64_t>& koff, DevBuf<uint16_t>& col16, DevBuf<int4>& gband) {
+    const size_t nbk = blocks.size();
+    ParZeros<uint16_t> c16((size_t)(koff[nbk] + kPad));
+    std::vector<int4> gb(nbk, make_int4(0, 0, 0, 0));
+    int bad = 0;
+#pragma omp parallel for schedule(dynamic, 256) reduction(+ : bad)
+    for (size_t q = 0; q < nbk; ++q) {
+        const int kb = hrp[blocks[q].x], nz = hrp[blocks[q].y] - kb;
+        if (nz == 0 || nz > kCAP) continue;  // chunked path: int32 columns
+        std::vector<int> u(hcol.begin() + kb, hcol.begin() + kb + nz);
+        std::sort(u.begin(), u.end());
+        int base[4] = {0, 0, 0, 0}, nbnd = 0;
+        for (int c : u) {
+            if (nbnd == 0 || c - base[nbnd - 1] >= kGatherBand) {
+                if (nbnd == 4) {
+                    nbnd = 5;
+                    break;
+                }
+                base[nbnd++] = c;
+            }
+        }
+        if (nbnd > 4) {
+            ++bad;
+            continue;
+        }
+        for (int t = nbnd; t < 4; ++t) base[t] = base[nbnd - 1];
+        gb[q] = make_int4(base[0], base[1], base[2], base[3]);
+        for (int j = 0; j < nz; ++j) {
+            const int c = hcol[kb + j];
+            int t = nbnd - 1;
+            while (c < base[t]) --t;
+            c16[koff[q] + j] = (uint16_t)((t << 14) | (c - base[t]));
+        }
+    }
+    if (bad == 0) {
+        col16.upload(c16.data(), c16.size());
+        gband.upload(gb.data(), gb.size());
+    }
+}
+
+// 32-byte block headers (two scalar loads per block):
+//   {r0, r1, koff, nnz}, {diag slot, tile lines | dvi flag << 16, value-table offset (-1),
+//   table size}
+// diag slot (square operators): tile position of line r0 / line_w when the lines of the
+// block's own rows are consecutive in its tile, so x[r] is read from the tile; else -1.
+// Also M.jac_extra_all / jac_extra_csr: the Jacobi operand bytes of the CSR-kernel rows.
+static std::vector<int4> block_headers(DevMatrix& M, const std::vector<int>& hrp, const BlockBuild& bb,
+                                       const std::vector<int64_t>& koff, const FormatHeaderInfo& fi) {
+    const size_t nbk = bb.blocks.size();
+    const bool square = M.square, tiled = M.tiled;
+    const int line_w = M.line_w;
+    std::vector<int4> hh(std::max<size_t>(2 * nbk, 2), make_int4(0, 0, 0, 0));
+    M.jac_extra_all = M.jac_extra_csr = 0;
+    for (size_t q = 0; q < nbk; ++q) {
+        const int2 b = bb.blocks[q];
+        const int t0 = bb.tile_ptr[q], nt = bb.tile_ptr[q + 1] - t0;
+        int dslot = -1;
+        if (square && nt > 0 && nt <= kCAP / line_w) {
+            const int ls = line_w == 8 ? 3 : 2;
+            const int l0 = b.x >> ls, l1 = (b.y - 1) >> ls;
+            const int* tl = bb.tile_lines.data() + t0;
+            const int pos = (int)(std::lower_bound(tl, tl + nt, l0) - tl);
+            bool ok = pos + (l1 - l0) < nt;
+            for (int k = 0; ok && k <= l1 - l0; ++k) ok = tl[pos + k] == l0 + k;
+            if (ok) dslot = pos;
+        }
+        hh[2 * q] = make_int4(b.x, b.y, (int)koff[q], hrp[b.y] - hrp[b.x]);
+        if (square) {  // Jacobi operands beyond b: 1/a_ii (table index or fp64), x[r]
+            const int64_t rows = b.y - b.x;
+            const int64_t e = rows * (fi.dvi_ok[q] ? 1 : 8) + (dslot < 0 ? 8 * rows : 0);
+            M.jac_extra_all += e;
+            if ((int)q >= bb.nb_skip) M.jac_extra_csr += e;
+        }
+        // rectangular (gather) operators: field 0 = the block's offset in the VI index stream
+        const int f0 = square ? dslot : tiled ? -1 : (fi.vofs.empty() ? 0 : (int)fi.vofs[q]);
+        hh[2 * q + 1] = make_int4(f0, nt | (fi.dvi_ok[q] ? kHdrDvi : 0), fi.vt_off[q], fi.vt_len[q]);
+    }
+    return hh;
+}
+
+// Format bytes of one default-variant SpMV (the kernel reads every lane slot of the
+// fixed-stride streams, so their padding counts) into M.csr_fmt_bytes / M.spmv_fmt_bytes.
+// With templates: the skipped blocks cost nothing; template rows cost 1 byte (id); the
+// table (offsets, values, headers, 1/a_ii) is read from HBM once -- every further
+// workgroup's staging copy of it is an L2 hit, not HBM traffic
+static void format_bytes(DevMatrix& M, const std::vector<int4>& hh, const std::vector<int2>& blocks) {
+    const int64_t n_rows = M.n_rows;
+    const bool tiled = M.tiled;
+    const int line_w = M.line_w;
+    const int64_t xy = 8 * (M.n_cols_local + M.plan.n_halo()) + 8 * n_rows;
+    int64_t fb = 2 * n_rows + xy, fb_tpl = xy;
+    if (M.tpl.n > 0)
+        fb_tpl += n_rows + 12 * (int64_t)M.tpl.n_ent + 12 * (int64_t)M.tpl.n;
+    for (size_t q = 0; q < blocks.size(); ++q) {
+        const int nz = hh[2 * q].w, nt = hh[2 * q + 1].y & 0xffff;
+        const int64_t fb0 = fb;
+        fb += 32;
+        if (nz == 0) continue;
+        if (nz > kCAP || (tiled && nt > kCAP / line_w)) {  // long row: CSR stream
+            fb += 12 * (int64_t)nz;
+            continue;
+        }
+        if (tiled) fb += 4 * (kCAP / line_w) + 2 * kCAP;  // tile ids, tile indices
+        else if (M.col16.p) fb += 2 * (int64_t)nz + 16;   // column codes, band bases
+        else fb += 4 * (int64_t)nz;                       // columns
+        if (hh[2 * q + 1].z >= 0)
+            fb += (tiled ? kCAP : gather_slots(nz) * kTPB) + 8 * (int64_t)hh[2 * q + 1].w;
+        else
+            fb += 8 * (int64_t)nz;
+        if ((int)q >= M.nb_skip) fb_tpl += fb - fb0 + 2 * (int64_t)(blocks[q].y - blocks[q].x);
+    }
+    M.csr_fmt_bytes = fb;
+    M.spmv_fmt_bytes = M.tpl.n > 0 ? fb_tpl : fb;
+}
+
+// Every device format from a CSR the caller keeps (H, never the member `host`):
+// Solver::setup runs this on a worker thread while the hierarchy thread still reads the same
+// CSR, and moves it into `host` after both are done.
+void DevMatrix::build_view(Context* c, const HostCSR& H, bool replicated_view) {
+    ctx = c;
+    replicated = replicated_view;
+    static const HostComm serial;  // rank 0 of 1: replicated matrices have no halo
+    const HostComm& comm = replicated ? serial : ctx->host;
+    const BuildKnobs knobs = read_build_knobs();
+    PhaseTimer tm(comm);
+    AMG_CHECK((int)H.row_starts.size() == comm.nranks + 1, "matrix row partition size");
+    AMG_CHECK((int)H.col_starts.size() == comm.nranks + 1, "matrix column partition size");
+    first_row = H.row_starts[comm.rank];
+    n_rows = H.nrows();
+    AMG_CHECK(n_rows == H.row_starts[comm.rank + 1] - first_row, "local row count mismatch");
+    first_col = H.col_starts[comm.rank];
+    n_cols_local = H.col_starts[comm.rank + 1] - first_col;
+    nnz = H.nnz();
+    AMG_CHECK(nnz < INT_MAX && n_rows < INT_MAX, "local matrix exceeds int32 indexing");
+    square = H.n_global_rows == H.n_global_cols && H.row_starts == H.col_starts;
+    plan = halo_plan_for_cols(comm, H);
+    if (send_map && !replicated)
+        for (int64_t& v : plan.send_idx) v = (*send_map)[v];
+    AMG_CHECK(n_cols_local + plan.n_halo() < INT_MAX, "too many columns for int32");
+    tm.lap("    build: halo plan");
+
+    std::vector<int> hrp;
+    hvec<int> hcol;
+    std::vector<uint8_t> cls;
+    local_columns(H, plan, first_col, n_cols_local, hrp, hcol, cls);
     rp.upload(hrp.data(), hrp.size());
     std::vector<double> di;
     if (square) {
-        std::vector<double> d = diagonal(comm, host);
+        std::vector<double> d = diagonal(comm, H);
         di.resize(n_rows);
 #pragma omp parallel for schedule(static)
         for (int64_t i = 0; i < n_rows; ++i) di[i] = 1.0 / d[i];
         dinv.upload(di.data(), di.size());
     }
-    // row templates: square operators whose templates cover every row, or at least half of
-    // the rows of a large operator (AMG_TPL_MIN_ROWS, default 16384; tests lower it)
     TplBuild tb;
-    n_tpl = n_tpl_ent = nb_skip = 0;
-    tpl_rows = 0;
-    if (square && n_rows > 0 && !blocks_only) {
-        const char* e = std::getenv("AMG_TPL_MIN_ROWS");
-        const int64_t min_rows = e ? std::atoll(e) : (int64_t)16384;
-        tb = build_templates(hrp, hcol, host.val, di, n_cols_local);
-        const bool use = tb.rows == n_rows || (n_rows >= min_rows && 2 * tb.rows >= n_rows);
-        if (!use) tb = TplBuild();
-    }
+    tpl = TplFormat{};
+    nb_skip = 0;
+    if (square && n_rows > 0 && !blocks_only) tb = select_templates(knobs, H, hrp, hcol, di, n_cols_local);
     tm.lap("    build: local columns, dinv, templates");
-    hcol.resize(nnz + kPad, 0);
-    {
-        std::vector<uint8_t> tplf;
-        if (!tb.hdr.empty()) {
-            tplf.resize(n_rows);
-            for (int64_t i = 0; i < n_rows; ++i) tplf[i] = tb.id[i] != kTplNone && cls[i] == 0;
-        }
-        // square operators: x tiles, one row per lane; short-row rectangular ones (gather
-        // path): up to kGatherRPB rows per lane (profiles/r2n: P0 x += P e 162 -> 95 us; R
-        // with 7+ entries per row was slower that way: R0 94 -> 106 us, sa27 R0 350 -> 415)
-        gather_rpb = !square && nnz <= 4 * n_rows ? kGatherRPB : 1;
-        const bool dev_fmt = device_formats();
-        // The format choices below (x tile or gather, 64- or 32-byte lines) read statistics of
-        // the 64-byte cut; r5 takes them from every 8th of its 64 row chunks (the whole
-        // operator below 65,536 rows) and cuts the operator once, at the chosen width.  Before,
-        // each choice cut the whole operator again: 0.6 s of sa27's setup.
-        constexpr int kSample = 8;
-        const BlockBuild s8 = build_row_blocks(hrp, hcol, cls, n_cols_local, plan.n_halo(),
-                                               tplf.empty() ? nullptr : &tplf, kTPB * gather_rpb, true, false, 8,
-                                               kSample);
-        // rectangular operators take the x-tile kernel when their blocks reuse x lines: at most
-        // 0.5 tile lines per nonzero.  Same-box A/B (profiles/r2y_rtile_*, r2z_rpb_*): 7-pt R0
-        // 106 -> 79 us (0.23 lines / nnz), R1 66 -> 53 (0.34), P0 (4 rows per lane, 0.06)
-        // 97 -> 80, P1 49 -> 39; sa27 P0 299 -> 234 (0.04), P1 33 -> 26; g3sub R0 24 -> 20
-        // (0.33), P0 19 -> 15; sa27 R1 122 -> 158 at 0.70 (a 297-entry block loading 210
-        // lines) stays on the gather kernel.
-        // AMG_RECT_TILE=0 / 1: never / always (A/B runs)
-        int64_t tile_lines_total = 0, tile_full = 0, sample_nnz = 0;
-        for (size_t q = 0; q + 1 < s8.tile_ptr.size(); ++q) {
-            const int nt = s8.tile_ptr[q + 1] - s8.tile_ptr[q];
-            tile_lines_total += nt;
-            tile_full += nt >= kTileLines;
-            sample_nnz += hrp[s8.blocks[q].y] - hrp[s8.blocks[q].x];
-        }
-        {
-            const char* e = std::getenv("AMG_RECT_TILE");
-            const int mode = e ? std::atoi(e) : -1;
-            tiled = square || (mode != 0 && (mode == 1 || 2 * tile_lines_total <= sample_nnz));
-        }
-        if (std::getenv("AMG_TRACE_BLOCKS")) {
-            const int64_t lines = tile_lines_total, full = tile_full;
-            std::fprintf(stderr, "[amg-blocks] %s rows %lld cols %lld nnz %lld sampled: blocks %zu lines %lld full %lld nnz %lld rpb %d\n",
-                         square ? "square" : tiled ? "rect-tiled" : "rect-gather", (long long)n_rows, (long long)n_cols_local, (long long)nnz,
-                         s8.blocks.size(), (long long)lines, (long long)full, (long long)sample_nnz, gather_rpb);
-        }
-        // x-tile line width: operators whose blocks, cut at 256 lines of
-        // 64 B, run close to the cap (>= 3/4 full on average: Galerkin operators,
-        // restrictions) are cut at 512 lines of 32 B (the 7-pt 256^3 A2: 40,250 -> 25,615
-        // blocks; R0: same-box 76 -> 70 us); P-like operators (few lines per block) keep
-        // 64-byte lines and their 1 KiB of line ids per block (sa27 P0: 234 us at 64 B, 263 at
-        // 32 B), and so do square operators the 32-byte cut saves < 20 % of the blocks (the
-        // 7-pt A1: 50,573 -> 46,841 blocks ran 144 -> 149 us; A2: 40,281 -> 25,640 ran 125 ->
-        // 102 us); restrictions gain either way (R0 91 -> 88 us at -9 %, R1 61 -> 52 at -33 %).
-        // AMG_TILE_LINE=8 / 4 forces the width.
-        // The gather kernel reads x from global memory: its blocks need only the kCAP-entry and
-        // row caps, not the 256-line tile cap.  sa27's R1 (270 entries per row over ~200 lines
-        // each) was cut into blocks of ~1 row by that cap: one lane summing while 255 idled.
-        int lw = 8;
-        const bool line_cap = tiled;
-        if (tiled && !s8.blocks.empty()) {
-            const char* e = std::getenv("AMG_TILE_LINE");
-            const int force = e ? std::atoi(e) : 0;
-            const bool tryhalf = force == 4 || (force != 8 && 4 * tile_lines_total >= 3 * (int64_t)kTileLines *
-                                                                                         (int64_t)s8.blocks.size());
-            if (tryhalf) {
-                bool take = force == 4 || !square;
-                if (!take) {
-                    const BlockBuild s4 = build_row_blocks(hrp, hcol, cls, n_cols_local, plan.n_halo(),
-                                                           tplf.empty() ? nullptr : &tplf, kTPB * gather_rpb, true,
-                                                           false, 4, kSample);
-                    take = 5 * s4.blocks.size() <= 4 * s8.blocks.size();
-                }
-                if (take) lw = 4;
-            }
-        }
-        tm.lap("    build: row blocks, sampled cuts");
-        BlockBuild bb = build_row_blocks(hrp, hcol, cls, n_cols_local, plan.n_halo(),
-                                         tplf.empty() ? nullptr : &tplf, kTPB * gather_rpb, line_cap, !dev_fmt, lw);
-        line_w = lw;
-        nb_int = bb.nb_int;
-        nb_bnd = bb.nb_bnd;
-        if (std::getenv("AMG_TRACE_BLOCKS"))
-            std::fprintf(stderr, "[amg-blocks]   %s, lines of %d B: %zu blocks\n", tiled ? "x tile" : "gather",
-                         8 * line_w, bb.blocks.size());
-        tm.lap("    build: row blocks + x tiles");
-        if (!tb.hdr.empty()) {
-            // rows of blocks the CSR kernel still runs are not the template kernel's
-            std::vector<char> keep(n_rows, 0);
-            for (int q = 0; q < bb.nb_skip; ++q)
-                for (int r = bb.blocks[q].x; r < bb.blocks[q].y; ++r) keep[r] = 1;
-            int64_t rows = 0;
-            for (int64_t i = 0; i < n_rows; ++i) {
-                if (!keep[i]) tb.id[i] = (uint8_t)kTplNone;
-                rows += tb.id[i] != kTplNone;
-            }
-            nb_skip = bb.nb_skip;
-            tpl_rows = rows;
-            n_tpl = (int)tb.hdr.size();
-            n_tpl_ent = (int)tb.off.size();
-            tpl_id.upload(tb.id.data(), tb.id.size());
-            tpl_id_host = tb.id;
-            tpl_hdr.upload(tb.hdr.data(), tb.hdr.size());
-            tpl_off.upload(tb.off.data(), tb.off.size());
-            tpl_val.upload(tb.val.data(), tb.val.size());
-            tpl_pd.upload(tb.pd.data(), tb.pd.size());
-            // x window: distinct offsets merged into bands while a gap is shorter than a
-            // workgroup's rows (a new band would load kTplRows more doubles than the gap)
-            std::vector<int> offs(tb.off);
-            std::sort(offs.begin(), offs.end());
-            offs.erase(std::unique(offs.begin(), offs.end()), offs.end());
-            std::vector<int2> bands;  // {lo, hi}
-            for (int o : offs) {
-                if (!bands.empty() && (int64_t)o - bands.back().y < kTplRows) bands.back().y = o;
-                else bands.push_back(make_int2(o, o));
-            }
-            // even band starts and lengths: slot pairs map to 16-byte aligned pairs of x
-            for (int2& bd : bands) bd.x &= ~1;
-            auto blen = [](const int2& bd) { return (int64_t)(kTplRows + bd.y - bd.x + 1) & ~(int64_t)1; };
-            int64_t w = 0;
-            for (const int2& bd : bands) w += blen(bd);
-            tpl_blo.clear();
-            tpl_bbase.clear();
-            tpl_win = tpl_wend = 0;
-            tpl_ldo.reset();
-            if ((int)bands.size() <= kTplBands && w <= kTplWin) {
-                std::vector<int> ldo(tb.off.size());
-                int base = 0;
-                for (const int2& bd : bands) {
-                    tpl_blo.push_back(bd.x);
-                    tpl_bbase.push_back(base);
-                    base += (int)blen(bd);
-                }
-                tpl_wend = bands.back().x + (int)blen(bands.back());
-                for (size_t k = 0; k < tb.off.size(); ++k) {
-                    const int o = tb.off[k];
-                    size_t q = 0;
-                    while (q + 1 < bands.size() && o > bands[q].y) ++q;
-                    ldo[k] = tpl_bbase[q] + (o - bands[q].x);
-                }
-                tpl_win = base;
-                tpl_ldo.upload(ldo.data(), ldo.size());
-                find_master_template(*this, tb, ldo);
-                // z-marching: the shift D (a multiple of kTplRows, taken from the band
-                // starts) under which the most window slots of a block are slots of the block
-                // D rows back; used when at least a quarter of the window is reused
-                const int nbd = (int)bands.size();
-                auto reuse_map = [&](int64_t D, std::vector<int>* map) {
-                    int cnt = 0;
-                    for (int q = 0; q < nbd; ++q) {
-                        const int len = (q + 1 < nbd ? tpl_bbase[q + 1] : base) - tpl_bbase[q];
-                        for (int i = 0; i < len; ++i) {
-                            const int64_t g = D + tpl_blo[q] + i;  // relative to the old r0
-                            int src = -1;
-                            for (int q2 = 0; q2 < nbd && src < 0; ++q2) {
-                                const int len2 = (q2 + 1 < nbd ? tpl_bbase[q2 + 1] : base) - tpl_bbase[q2];
-                                const int64_t j = g - tpl_blo[q2];
-                                if (j >= 0 && j < len2) src = tpl_bbase[q2] + (int)j;
-                            }
-                            if (map) (*map)[tpl_bbase[q] + i] = src;
-                            cnt += src >= 0;
-                        }
-                    }
-                    return cnt;
-                };
-                int64_t bestD = 0;
-                int best = 0;
-                std::vector<int64_t> cand;
-                for (int q = 0; q < nbd; ++q) {
-                    cand.push_back(std::abs((int64_t)tpl_blo[q]));
-                    for (int q2 = q + 1; q2 < nbd; ++q2) cand.push_back((int64_t)tpl_blo[q2] - tpl_blo[q]);
-                }
-                for (int64_t D : cand) {
-                    D -= D % kTplRows;
-                    if (D <= 0 || D / kTplRows > INT_MAX / 2) continue;
-                    const int c = reuse_map(D, nullptr);
-                    if (c > best) best = c, bestD = D;
-                }
-                tpl_march_s = 0;
-                tpl_wsrc.reset();
-                // 16-byte pair loads: an even row count keeps every pair inside or outside x
-                if (bestD > 0 && 4 * best >= base && n_rows % 2 == 0) {
-                    std::vector<int> map(base, -1);
-                    reuse_map(bestD, &map);
-                    tpl_march_s = (int)(bestD / kTplRows);
-                    tpl_wsrc.upload(map.data(), map.size());
-                }
-            }
-        } else {
-            tpl_blo.clear();
-            tpl_bbase.clear();
-            tpl_win = tpl_wend = 0;
-            tpl_ldo.reset();
-            tpl_id.reset();
-            tpl_id_host.clear();
-            tpl_hdr.reset();
-            tpl_off.reset();
-            tpl_val.reset();
-            tpl_pd.reset();
-        }
-        if (tpl_win == 0) {
-            tpl_mne = 0;
-            tpl_mmask.reset();
-        }
-        tm.lap("    build: template window / march");
-        blocks.upload(bb.blocks.data(), bb.blocks.size());
-        const size_t nbk = bb.blocks.size();
-        // device col / val: block-aligned copies -- block q's entries at an even offset
-        // koff[q] (16-byte aligned values), so the kernel reads them as (2t, 2t + 1) pairs
-        std::vector<int64_t> koff(nbk + 1, 0);
-        for (size_t q = 0; q < nbk; ++q)
-            koff[q + 1] = koff[q] + (int64_t)(hrp[bb.blocks[q].y] - hrp[bb.blocks[q].x] + 1) / 2 * 2;
-        AMG_CHECK(koff[nbk] + kPad < INT_MAX, "local matrix exceeds int32 indexing");
-        std::vector<int> vt_off, vt_len;
-        std::vector<char> dvi_ok;
-        std::vector<int64_t> vofs;
-        if (dev_fmt) {
-            // per-nonzero streams built on the GPU from one upload of the CSR (formats.hip)
-            FormatHeaderInfo fi;
-            build_formats_device(*this, hrp, hcol, host.val, bb.blocks, bb.tile_ptr, bb.tile_lines, koff, fi);
-            vt_off = std::move(fi.vt_off);
-            vt_len = std::move(fi.vt_len);
-            dvi_ok = std::move(fi.dvi_ok);
-            vofs = std::move(fi.vofs);
-            tm.lap("    build: device col / val / tiles / value index / row ends");
-        } else {
-            {
-                ParZeros<int> cb((size_t)(koff[nbk] + kPad));
-                ParZeros<double> vb(cb.size());
-#pragma omp parallel for schedule(dynamic, 256)
-                for (size_t q = 0; q < nbk; ++q) {
-                    const int kb = hrp[bb.blocks[q].x], nz = hrp[bb.blocks[q].y] - kb;
-                    std::copy(hcol.begin() + kb, hcol.begin() + kb + nz, cb.begin() + koff[q]);
-                    std::copy(host.val.begin() + kb, host.val.begin() + kb + nz, vb.begin() + koff[q]);
-                }
-                col.upload(cb.data(), cb.size());
-                val.upload(vb.data(), vb.size());
-            }
-            if (tiled) {  // x tiles: the x-tile kernel only
-                // x-tile line ids at a fixed stride (kCAP / line_w per block, padded with the block's
-                // last line), so the kernel loads them without waiting for the block header
-                const int tlb = kCAP / line_w;
-                ParZeros<int> fx(std::max<size_t>(nbk, 1) * tlb);
-#pragma omp parallel for schedule(static)
-                for (size_t q = 0; q < nbk; ++q) {
-                    const int t0 = bb.tile_ptr[q], nt = bb.tile_ptr[q + 1] - t0;
-                    if (nt <= 0 || nt > tlb) continue;
-                    for (int j = 0; j < tlb; ++j)
-                        fx[q * tlb + j] = bb.tile_lines[t0 + std::min(j, nt - 1)];
-                }
-                tile_fixed.upload(fx.data(), fx.size());
-                // lane-major per block (lane_pos): lane t's 8 indices are 16 contiguous bytes,
-                // one 16-byte load per lane
-                ParZeros<uint16_t> perm(std::max<size_t>(nbk, 1) * kCAP);
-#pragma omp parallel for schedule(static)
-                for (size_t q = 0; q < nbk; ++q) {
-                    const int kb = hrp[bb.blocks[q].x], nz = hrp[bb.blocks[q].y] - kb;
-                    if (nz > kCAP) continue;
-                    for (int j = 0; j < nz; ++j)
-                        perm[q * kCAP + lane_pos(j, kCAP / kTPB)] = bb.lcol[kb + j];
-                }
-                lcol.upload(perm.data(), perm.size());
-            } else {
-                tile_fixed.reset();
-                lcol.reset();
-            }
-            tm.lap("    build: col / val / tile layouts");
-            std::vector<uint8_t> hdvi;
-            build_value_index(*this, host, hrp, bb, vt_off, vt_len, hdvi, dvi_ok, vofs);
-            if (n_vi_blocks > 0 && square) dvi.upload(hdvi.data(), hdvi.size());
-            else dvi.reset();
-            tm.lap("    build: value index");
-            {
-                // per row: end of its nonzeros relative to its block's first (<= kCAP: 16 bits)
-                std::vector<uint16_t> re((size_t)n_rows + 1, 0);
-                for (size_t q = 0; q < nbk; ++q) {
-                    const int2 b = bb.blocks[q];
-                    if (hrp[b.y] - hrp[b.x] > kCAP) continue;
-                    for (int r = b.x; r < b.y; ++r) re[r] = (uint16_t)(hrp[r + 1] - hrp[b.x]);
-                }
-                rend.upload(re.data(), re.size());
-            }
-        }
-        // gather operators: 16-bit column codes when every block's columns fit in <= 4
-        // bands of kGatherBand: a structured P / R block reads three
-        // planes' worth of columns, each a narrow band.  Lossless: the kernel decodes
-        // base[code >> 14] + (code & 0x3fff), the same column.
-        col16.reset();
-        gband.reset();
-        if (!tiled && nbk > 0) {
-            ParZeros<uint16_t> c16((size_t)(koff[nbk] + kPad));
-            std::vector<int4> gb(nbk, make_int4(0, 0, 0, 0));
-            int bad = 0;
-#pragma omp parallel for schedule(dynamic, 256) reduction(+ : bad)
-            for (size_t q = 0; q < nbk; ++q) {
-                const int kb = hrp[bb.blocks[q].x], nz = hrp[bb.blocks[q].y] - kb;
-                if (nz == 0 || nz > kCAP) continue;  // chunked path: int32 columns
-                std::vector<int> u(hcol.begin() + kb, hcol.begin() + kb + nz);
-                std::sort(u.begin(), u.end());
-                int base[4] = {0, 0, 0, 0}, nbnd = 0;
-                for (int c : u) {
-                    if (nbnd == 0 || c - base[nbnd - 1] >= kGatherBand) {
-                        if (nbnd == 4) {
-                            nbnd = 5;
-                            break;
-                        }
-                        base[nbnd++] = c;
-                    }
-                }
-                if (nbnd > 4) {
-                    ++bad;
-                    continue;
-                }
-                for (int t = nbnd; t < 4; ++t) base[t] = base[nbnd - 1];
-                gb[q] = make_int4(base[0], base[1], base[2], base[3]);
-                for (int j = 0; j < nz; ++j) {
-                    const int c = hcol[kb + j];
-                    int t = nbnd - 1;
-                    while (c < base[t]) --t;
-                    c16[koff[q] + j] = (uint16_t)((t << 14) | (c - base[t]));
-                }
-            }
-            if (bad == 0) {
-                col16.upload(c16.data(), c16.size());
-                gband.upload(gb.data(), gb.size());
-            }
-        }
-        // 32-byte block headers (two scalar loads per block):
-        //   {r0, r1, koff, nnz}, {diag slot, tile lines | dvi flag << 16, value-table offset (-1),
-        //   table size}
-        // diag slot (square operators): tile position of line r0 / line_w when the lines of the
-        // block's own rows are consecutive in its tile, so x[r] is read from the tile; else -1
-        std::vector<int4> hh(std::max<size_t>(2 * nbk, 2), make_int4(0, 0, 0, 0));
-        jac_extra_all = jac_extra_csr = 0;
-        for (size_t q = 0; q < nbk; ++q) {
-            const int2 b = bb.blocks[q];
-            const int t0 = bb.tile_ptr[q], nt = bb.tile_ptr[q + 1] - t0;
-            int dslot = -1;
-            if (square && nt > 0 && nt <= kCAP / line_w) {
-                const int ls = line_w == 8 ? 3 : 2;
-                const int l0 = b.x >> ls, l1 = (b.y - 1) >> ls;
-                const int* tl = bb.tile_lines.data() + t0;
-                const int pos = (int)(std::lower_bound(tl, tl + nt, l0) - tl);
-                bool ok = pos + (l1 - l0) < nt;
-                for (int k = 0; ok && k <= l1 - l0; ++k) ok = tl[pos + k] == l0 + k;
-                if (ok) dslot = pos;
-            }
-            hh[2 * q] = make_int4(b.x, b.y, (int)koff[q], hrp[b.y] - hrp[b.x]);
-            if (square) {  // Jacobi operands beyond b: 1/a_ii (table index or fp64), x[r]
-                const int64_t rows = b.y - b.x;
-                const int64_t e = rows * (dvi_ok[q] ? 1 : 8) + (dslot < 0 ? 8 * rows : 0);
-                jac_extra_all += e;
-                if ((int)q >= bb.nb_skip) jac_extra_csr += e;
-            }
-            // rectangular (gather) operators: field 0 = the block's offset in the VI index stream
-            const int f0 = square ? dslot : tiled ? -1 : (vofs.empty() ? 0 : (int)vofs[q]);
-            hh[2 * q + 1] = make_int4(f0, nt | (dvi_ok[q] ? kHdrDvi : 0), vt_off[q], vt_len[q]);
-        }
-        hdr.upload(hh.data(), hh.size());
-        // measured (profiles/r1m_variants.txt): x tiles in XCD order on square operators (A0
-        // -6..8%, A1 -6..8%, A2 +1% vs plain order; gathers are 1.3-1.9x slower); gathers in
-        // XCD order on the rectangular P / R (R0 -10% vs plain order)
-        default_variant = tiled ? 2 : (4 | 2);
-        // format bytes of one default-variant SpMV (the kernel reads every lane slot of the
-        // fixed-stride streams, so their padding counts)
-        // with templates: the skipped blocks cost nothing; template rows cost 1 byte (id); the
-        // table (offsets, values, headers, 1/a_ii) is read from HBM once -- every further
-        // workgroup's staging copy of it is an L2 hit, not HBM traffic
-        const int64_t xy = 8 * (n_cols_local + plan.n_halo()) + 8 * n_rows;
-        int64_t fb = 2 * n_rows + xy, fb_tpl = xy;
-        if (n_tpl > 0)
-            fb_tpl += n_rows + 12 * (int64_t)n_tpl_ent + 12 * (int64_t)n_tpl;
-        for (size_t q = 0; q < nbk; ++q) {
-            const int nz = hh[2 * q].w, nt = hh[2 * q + 1].y & 0xffff;
-            const int64_t fb0 = fb;
-            fb += 32;
-            if (nz == 0) continue;
-            if (nz > kCAP || (tiled && nt > kCAP / line_w)) {  // long row: CSR stream
-                fb += 12 * (int64_t)nz;
-                continue;
-            }
-            if (tiled) fb += 4 * (kCAP / line_w) + 2 * kCAP;  // tile ids, tile indices
-            else if (col16.p) fb += 2 * (int64_t)nz + 16;  // column codes, band bases
-            else fb += 4 * (int64_t)nz;                     // columns
-            if (hh[2 * q + 1].z >= 0)
-                fb += (tiled ? kCAP : gather_slots(nz) * kTPB) + 8 * (int64_t)hh[2 * q + 1].w;
-            else
-                fb += 8 * (int64_t)nz;
-            if ((int)q >= nb_skip) fb_tpl += fb - fb0 + 2 * (int64_t)(bb.blocks[q].y - bb.blocks[q].x);
-        }
-        csr_fmt_bytes = fb;
-        spmv_fmt_bytes = n_tpl > 0 ? fb_tpl : fb;
-        tm.lap("    build: row ends, headers");
+    hcol.resize(nnz + kPad, 0);  // within the capacity local_columns reserved
+
+    std::vector<uint8_t> tplf;
+    if (!tb.hdr.empty()) {
+        tplf.resize(n_rows);
+        for (int64_t i = 0; i < n_rows; ++i) tplf[i] = tb.id[i] != kTplNone && cls[i] == 0;
     }
+    const std::vector<uint8_t>* tplf_p = tplf.empty() ? nullptr : &tplf;
+    // square operators: x tiles, one row per lane; short-row rectangular ones (gather
+    // path): up to kGatherRPB rows per lane (profiles/r2n: P0 x += P e 162 -> 95 us; R
+    // with 7+ entries per row was slower that way: R0 94 -> 106 us, sa27 R0 350 -> 415)
+    gather_rpb = !square && nnz <= 4 * n_rows ? kGatherRPB : 1;
+    const bool dev_fmt = device_formats();
+    const CutChoice cut = choose_cut(knobs, hrp, hcol, cls, tplf_p, n_cols_local, plan.n_halo(), square, gather_rpb);
+    tiled = cut.tiled;
+    tm.lap("    build: row blocks, sampled cuts");
+    // The gather kernel reads x from global memory: its blocks need only the kCAP-entry and
+    // row caps, not the 256-line tile cap.  sa27's R1 (270 entries per row over ~200 lines
+    // each) was cut into blocks of ~1 row by that cap: one lane summing while 255 idled.
+    const bool line_cap = tiled;
+    BlockBuild bb = build_row_blocks(hrp, hcol, cls, n_cols_local, plan.n_halo(), tplf_p, kTPB * gather_rpb,
+                                     line_cap, !dev_fmt, cut.line_w);
+    line_w = cut.line_w;
+    nb_int = bb.nb_int;
+    nb_bnd = bb.nb_bnd;
+    if (knobs.trace_blocks)
+        std::fprintf(stderr, "[amg-blocks]   %s, lines of %d B: %zu blocks\n", tiled ? "x tile" : "gather",
+                     8 * line_w, bb.blocks.size());
+    tm.lap("    build: row blocks + x tiles");
+
+    if (!tb.hdr.empty()) {
+        nb_skip = bb.nb_skip;
+        upload_templates(tpl, tb, bb, n_rows);
+        const std::vector<int> ldo = tpl_window(tpl, tb);
+        if (tpl.win > 0) {
+            if (knobs.tpl_master) tpl.master = find_master_template(tb, ldo);
+            tpl_march(tpl, n_rows);
+        }
+    }
+    tm.lap("    build: template window / march");
+
+    blocks.upload(bb.blocks.data(), bb.blocks.size());
+    const size_t nbk = bb.blocks.size();
+    // device col / val: block-aligned copies -- block q's entries at an even offset
+    // koff[q] (16-byte aligned values), so the kernel reads them as (2t, 2t + 1) pairs
+    std::vector<int64_t> koff(nbk + 1, 0);
+    for (size_t q = 0; q < nbk; ++q)
+        koff[q + 1] = koff[q] + (int64_t)(hrp[bb.blocks[q].y] - hrp[bb.blocks[q].x] + 1) / 2 * 2;
+    AMG_CHECK(koff[nbk] + kPad < INT_MAX, "local matrix exceeds int32 indexing");
+    FormatHeaderInfo fi;
+    if (dev_fmt) {
+        // per-nonzero streams built on the GPU from one upload of the CSR (formats.hip)
+        build_formats_device(*this, hrp, hcol, H.val, bb.blocks, bb.tile_ptr, bb.tile_lines, koff, fi);
+        tm.lap("    build: device col / val / tiles / value index / row ends");
+    } else {
+        host_block_streams(*this, tm, H, hrp, hcol, bb, koff, fi);
+    }
+    col16.reset();
+    gband.reset();
+    if (!tiled && nbk > 0) gather_codes(hrp, hcol, bb.blocks, koff, col16, gband);
+    const std::vector<int4> hh = block_headers(*this, hrp, bb, koff, fi);
+    hdr.upload(hh.data(), hh.size());
+    // measured (profiles/r1m_variants.txt): x tiles in XCD order on square operators (A0
+    // -6..8%, A1 -6..8%, A2 +1% vs plain order; gathers are 1.3-1.9x slower); gathers in
+    // XCD order on the rectangular P / R (R0 -10% vs plain order)
+    default_variant = tiled ? KV_XCD : (KV_GATHER | KV_XCD);
+    format_bytes(*this, hh, bb.blocks);
+    tm.lap("    build: row ends, headers");
+
     std::vector<int> sidx(plan.send_idx.begin(), plan.send_idx.end());
     send_idx.upload(sidx.data(), sidx.size());
     send_buf.alloc(sidx.size());
@@ -1144,38 +1222,44 @@ void DevMatrix::build_view(Context* c, const HostCSR& host, bool replicated_view
     }
 }
 
-// The one-kernel sweep's sliced ELL (hybrid_gs_kernel): every entry of the ELL slabs, with a
-// value dictionary when the local operator takes <= 256 distinct values.  Built with the GS
-// blocks unless the operator runs split sweeps (4.2c), whose passes never read it; then on
-// first use (a norm-carrying forward sweep: Solver::setup builds it for level 0).  r5: sa27's
-// level-1 / level-2 GS builds spent ~1.9 s of an 8.1 s setup mostly here.
-// The split sweep's old-value pass for direction d (0 forward, 1 backward): this operator
-// without the sweep's in-chunk new-value couplings, as a CSR-block matrix of its own (4.2c).
-// Collective on N ranks (its halo plan); never inside a graph capture (Solver::setup builds
-// what the cycle needs).
-void DevMatrix::ensure_gs_pass(int d) {
-    if (gs_old[d]) return;
-    const HostCSR& host = host_image();  // the member, or the CSR a worker builds from
-    AMG_CHECK(gs_split && gs_block > 0, "hybrid GS: no split sweep for this operator");
-    AMG_CHECK(!ctx->capturing, "hybrid GS: split pass requested inside a graph capture");
-    const int64_t B = gs_block, clo = first_col, chi = first_col + n_cols_local;
-    auto is_new = [&](int64_t i, int64_t gc) {
+// The GS chunks of an operator's local rows (global multiples of B clipped to the rank) and
+// the in-chunk new-value couplings of a sweep in direction d (0 forward, 1 backward): row i
+// (local ids) with global column gc, forward cs <= j < i, backward i < j < ce
+// (hybrid_gs_kernel's [lo, hi))
+struct GsChunks {
+    int64_t first_row, n_rows, clo, chi, B;
+    explicit GsChunks(const DevMatrix& M)
+        : first_row(M.first_row), n_rows(M.n_rows), clo(M.first_col), chi(M.first_col + M.n_cols_local),
+          B(M.gs.block) {}
+    bool is_new(int d, int64_t i, int64_t gc) const {
         if (gc < clo || gc >= chi) return false;
         const int64_t j = gc - clo, g = first_row + i;
         const int64_t cs = std::max<int64_t>(0, (g / B) * B - first_row);
         const int64_t ce = std::min<int64_t>(n_rows, (g / B + 1) * B - first_row);
         return d == 0 ? (j >= cs && j < i) : (j > i && j < ce);
-    };
+    }
+};
+
+// The split sweep's old-value pass for direction d (0 forward, 1 backward): this operator
+// without the sweep's in-chunk new-value couplings, as a CSR-block matrix of its own (4.2c).
+// Collective on N ranks (its halo plan); never inside a graph capture (Solver::setup builds
+// what the cycle needs).
+void DevMatrix::ensure_gs_pass(int d) {
+    if (gs.split.old[d]) return;
+    const HostCSR& H = host_image();  // the member `host`, or the CSR a worker builds from
+    AMG_CHECK(gs.split.on && gs.block > 0, "hybrid GS: no split sweep for this operator");
+    AMG_CHECK(!ctx->capturing, "hybrid GS: split pass requested inside a graph capture");
+    const GsChunks ch(*this);
     HostCSR h;
-    h.n_global_rows = host.n_global_rows;
-    h.n_global_cols = host.n_global_cols;
-    h.row_starts = host.row_starts;
-    h.col_starts = host.col_starts;
+    h.n_global_rows = H.n_global_rows;
+    h.n_global_cols = H.n_global_cols;
+    h.row_starts = H.row_starts;
+    h.col_starts = H.col_starts;
     h.rp.assign((size_t)n_rows + 1, 0);
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < n_rows; ++i) {
         int64_t c = 0;
-        for (int64_t k = host.rp[i]; k < host.rp[i + 1]; ++k) c += !is_new(i, host.col[k]);
+        for (int64_t k = H.rp[i]; k < H.rp[i + 1]; ++k) c += !ch.is_new(d, i, H.col[k]);
         h.rp[i + 1] = c;
     }
     for (int64_t i = 0; i < n_rows; ++i) h.rp[i + 1] += h.rp[i];
@@ -1184,32 +1268,37 @@ void DevMatrix::ensure_gs_pass(int d) {
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < n_rows; ++i) {
         int64_t o = h.rp[i];
-        for (int64_t k = host.rp[i]; k < host.rp[i + 1]; ++k)
-            if (!is_new(i, host.col[k])) {
-                h.col[o] = host.col[k];
-                h.val[o] = host.val[k];
+        for (int64_t k = H.rp[i]; k < H.rp[i + 1]; ++k)
+            if (!ch.is_new(d, i, H.col[k])) {
+                h.col[o] = H.col[k];
+                h.val[o] = H.val[k];
                 ++o;
             }
     }
     // CSR blocks only: no row templates (and so no windows, masks or march tables) are built
     // for the pass's operator, and its format is set before the build -- no
     // format_generation bump, no captured graph goes stale
-    gs_old[d] = std::make_unique<DevMatrix>();
-    gs_old[d]->blocks_only = true;
-    gs_old[d]->format = AMG_FORMAT_BLOCKS;
-    gs_old[d]->build(ctx, std::move(h), replicated);
+    gs.split.old[d] = std::make_unique<DevMatrix>();
+    gs.split.old[d]->blocks_only = true;
+    gs.split.old[d]->format = AMG_FORMAT_BLOCKS;
+    gs.split.old[d]->build(ctx, std::move(h), replicated);
 }
 
+// The one-kernel sweep's sliced ELL (hybrid_gs_kernel): every entry of the ELL slabs, with a
+// value dictionary when the local operator takes <= 256 distinct values.  Built with the GS
+// blocks unless the operator runs split sweeps (4.2c), whose passes never read it; then on
+// first use (a norm-carrying forward sweep: Solver::setup builds it for level 0).  r5: sa27's
+// level-1 / level-2 GS builds spent ~1.9 s of an 8.1 s setup mostly here.
 void DevMatrix::ensure_gs_ell() {
-    if (gs_ell_built) return;
-    const HostCSR& host = host_image();  // the member, or the CSR a worker builds from
+    if (gs.ell_built) return;
+    const HostCSR& H = host_image();  // the member `host`, or the CSR a worker builds from
     AMG_CHECK(!ctx->capturing, "hybrid GS: sliced ELL requested inside a graph capture");
     const int64_t clo = first_col, chi = first_col + n_cols_local;
     auto local_col = [&](int64_t g) -> int {
         return g >= clo && g < chi ? (int)(g - clo) : (int)(n_cols_local + plan.find(g));
     };
-    const std::vector<int4>& slabs = gs_slabs_host;
-    const int64_t cells = gs_cells;
+    const std::vector<int4>& slabs = gs.slabs_host;
+    const int64_t cells = gs.cells;
     std::vector<int> sc((size_t)(cells + 4) * 64, -1);
     std::vector<double> sv(sc.size(), 0.0);
 #pragma omp parallel for schedule(dynamic, 64)
@@ -1217,10 +1306,10 @@ void DevMatrix::ensure_gs_ell() {
         const int4 sl = slabs[q];
         for (int l = 0; l < sl.y; ++l) {
             const int64_t i = sl.x + l;
-            for (int64_t k = host.rp[i]; k < host.rp[i + 1]; ++k) {
-                const size_t at = ((size_t)sl.z + (size_t)(k - host.rp[i])) * 64 + l;
-                sc[at] = local_col(host.col[k]);
-                sv[at] = host.val[k];
+            for (int64_t k = H.rp[i]; k < H.rp[i + 1]; ++k) {
+                const size_t at = ((size_t)sl.z + (size_t)(k - H.rp[i])) * 64 + l;
+                sc[at] = local_col(H.col[k]);
+                sv[at] = H.val[k];
             }
         }
     }
@@ -1228,7 +1317,7 @@ void DevMatrix::ensure_gs_ell() {
     // thread scans a chunk into a small set and gives up past 256
     std::vector<uint64_t> dict;
     {
-        const int64_t nz = (int64_t)host.val.size();
+        const int64_t nz = (int64_t)H.val.size();
         std::atomic<bool> over{false};
 #pragma omp parallel
         {
@@ -1237,7 +1326,7 @@ void DevMatrix::ensure_gs_ell() {
             for (int64_t k = 0; k < nz; ++k) {
                 if (over.load(std::memory_order_relaxed)) continue;
                 uint64_t bits;
-                std::memcpy(&bits, &host.val[k], sizeof(bits));
+                std::memcpy(&bits, &H.val[k], sizeof(bits));
                 if (std::find(mine.begin(), mine.end(), bits) == mine.end()) {
                     mine.push_back(bits);
                     if (mine.size() > 256) over.store(true, std::memory_order_relaxed);
@@ -1250,8 +1339,8 @@ void DevMatrix::ensure_gs_ell() {
         dict.erase(std::unique(dict.begin(), dict.end()), dict.end());
         if (over.load() || dict.size() > 256) dict.clear();
     }
-    gs_ndict = (int)dict.size();
-    if (gs_ndict > 0) {
+    gs.ndict = (int)dict.size();
+    if (gs.ndict > 0) {
         std::vector<uint8_t> vid(sc.size(), 0);
 #pragma omp parallel for schedule(dynamic, 64)
         for (size_t q = 0; q < slabs.size(); ++q) {
@@ -1268,26 +1357,25 @@ void DevMatrix::ensure_gs_ell() {
         }
         std::vector<double> tab(dict.size());
         std::memcpy(tab.data(), dict.data(), sizeof(double) * dict.size());
-        gs_vid.upload(vid.data(), vid.size());
-        gs_vtab.upload(tab.data(), tab.size());
-        gs_val.reset();
+        gs.vid.upload(vid.data(), vid.size());
+        gs.vtab.upload(tab.data(), tab.size());
+        gs.val.reset();
     } else {
-        gs_vid.reset();
-        gs_vtab.reset();
-        gs_val.upload(sv.data(), sv.size());
+        gs.vid.reset();
+        gs.vtab.reset();
+        gs.val.upload(sv.data(), sv.size());
     }
-    gs_col.upload(sc.data(), sc.size());
-    gs_ell_built = true;
+    gs.col.upload(sc.data(), sc.size());
+    gs.ell_built = true;
 }
 
-void DevMatrix::ensure_gs_blocks(int64_t B) {
-    const HostCSR& host = host_image();  // the member, or the CSR a worker builds from
-    AMG_CHECK(square, "hybrid GS needs a square matrix");
-    AMG_CHECK(B >= 1 && B <= 64, "hybrid GS block must be in [1, 64]");
-    if (gs_block == B) return;
-    const int64_t clo = first_col, chi = first_col + n_cols_local;
-    // l1 diagonal of every row: d_i = a_ii + sum of |a_ij| outside the row's chunk (global
-    // multiples of B clipped to the rank), summed in CSR order like the oracle
+// ---- the stages of DevMatrix::ensure_gs_blocks, in the order it runs them.  H is the
+// operator's host image.
+
+// l1 diagonal of every row: 1 / d_i, d_i = a_ii + sum of |a_ij| outside the row's chunk (global
+// multiples of B clipped to the rank), summed in CSR order like the oracle
+static std::vector<double> gs_l1_diagonal(const HostCSR& H, int64_t first_row, int64_t B) {
+    const int64_t n_rows = H.nrows();
     std::vector<double> di(n_rows);
     std::atomic<bool> zero_row{false};
 #pragma omp parallel for schedule(static)
@@ -1296,132 +1384,110 @@ void DevMatrix::ensure_gs_blocks(int64_t B) {
         const int64_t cs = std::max<int64_t>(first_row, g / B * B);
         const int64_t ce = std::min(first_row + n_rows, (g / B + 1) * B);
         double l1 = 0.0, d = 0.0;
-        for (int64_t k = host.rp[i]; k < host.rp[i + 1]; ++k) {
-            const int64_t gc = host.col[k];
-            if (gc < cs || gc >= ce) l1 += std::fabs(host.val[k]);
-            if (gc == g) d = host.val[k];
+        for (int64_t k = H.rp[i]; k < H.rp[i + 1]; ++k) {
+            const int64_t gc = H.col[k];
+            if (gc < cs || gc >= ce) l1 += std::fabs(H.val[k]);
+            if (gc == g) d = H.val[k];
         }
         if (d == 0.0 && l1 == 0.0) zero_row.store(true, std::memory_order_relaxed);
         di[i] = 1.0 / (d + l1);
     }
     AMG_CHECK(!zero_row.load(), "hybrid GS: zero row");
-    // GS templates: a 512-row block runs on tpl_gs_kernel when every row has
-    // a row template (all columns local) and the (template, l1 diagonal) pairs fit the table.
-    // Chunks must not straddle a wave's 64-row group: first_row % 64 == 0 and B | 64.
-    std::vector<char> tblk;
-    n_gs_tpl = n_gs_tblk = 0;
-    gs_tid.reset();
-    gs_thdr.reset();
-    gs_tdl.reset();
-    gs_tblocks.reset();
-    gs_tcvm.reset();
-    gs_tcvp.reset();
-    gs_tcf.reset();
-    gs_tkem.reset();
-    gs_tkep.reset();
-    gs_tmask.reset();
-    gs_racc.reset();
-    {
-        const char* e = std::getenv("AMG_GS_TEMPLATES");
-        const bool allow = !(e && std::atoi(e) == 0);
-        // the template kernels take one chain coupling per row: every template's in-chunk
-        // offsets (0 < |o| < B) must be -1 / +1 only
-        std::vector<int> hdrs, toff;
-        std::vector<double> tval;
-        bool shape_ok = n_tpl > 0 && tpl_win > 0;
-        if (shape_ok) {
-            hdrs.resize(n_tpl);
-            toff.resize(n_tpl_ent);
-            tval.resize(n_tpl_ent);
-            HIP_CHECK(hipMemcpy(hdrs.data(), tpl_hdr.p, sizeof(int) * n_tpl, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(toff.data(), tpl_off.p, sizeof(int) * n_tpl_ent, hipMemcpyDeviceToHost));
-            HIP_CHECK(hipMemcpy(tval.data(), tpl_val.p, sizeof(double) * n_tpl_ent, hipMemcpyDeviceToHost));
-            for (int o : toff)
-                if (o != 0 && o != -1 && o != 1 && std::llabs(o) < B) shape_ok = false;
+    return di;
+}
+
+// GS templates: a 512-row block runs on tpl_gs_kernel when every row has
+// a row template (all columns local) and the (template, l1 diagonal) pairs fit the table.
+// Chunks must not straddle a wave's 64-row group: first_row % 64 == 0 and B | 64.
+// Fills G from the row templates' host table; returns per 512-row block 1 = on the template
+// kernel (empty: none is).
+static std::vector<char> gs_templates(GsFormat::Tpl& G, const TplFormat& T, const std::vector<double>& di,
+                                      int64_t first_row, int64_t B) {
+    const int64_t n_rows = (int64_t)di.size();
+    // the template kernels take one chain coupling per row: every template's in-chunk
+    // offsets (0 < |o| < B) must be -1 / +1 only
+    bool shape_ok = T.n > 0 && T.win > 0;
+    for (int o : T.off_host)
+        if (o != 0 && o != -1 && o != 1 && std::llabs(o) < B) shape_ok = false;
+    if (!shape_ok || first_row % 64 != 0 || 64 % B != 0 || (int64_t)T.id_host.size() != n_rows) return {};
+    std::vector<uint8_t> gid((size_t)n_rows, (uint8_t)kTplNone);
+    std::vector<std::vector<std::pair<uint64_t, int>>> by_tpl(T.n);
+    std::vector<int> gbase;
+    std::vector<double> gdl;
+    for (int64_t i = 0; i < n_rows; ++i) {
+        const int t = T.id_host[i];
+        if (t == kTplNone) continue;
+        uint64_t bits;
+        std::memcpy(&bits, &di[i], sizeof(bits));
+        int found = -1;
+        for (const auto& pr : by_tpl[t])
+            if (pr.first == bits) {
+                found = pr.second;
+                break;
+            }
+        if (found < 0) {
+            if ((int)gbase.size() >= kTplMax) return {};
+            found = (int)gbase.size();
+            gbase.push_back(t);
+            gdl.push_back(di[i]);
+            by_tpl[t].push_back({bits, found});
         }
-        if (allow && shape_ok && first_row % 64 == 0 && 64 % B == 0 &&
-            (int64_t)tpl_id_host.size() == n_rows) {
-            std::vector<uint8_t> gid((size_t)n_rows, (uint8_t)kTplNone);
-            std::vector<std::vector<std::pair<uint64_t, int>>> by_tpl(n_tpl);
-            std::vector<int> gbase;
-            std::vector<double> gdl;
-            bool ok = true;
-            for (int64_t i = 0; i < n_rows && ok; ++i) {
-                const int t = tpl_id_host[i];
-                if (t == kTplNone) continue;
-                uint64_t bits;
-                std::memcpy(&bits, &di[i], sizeof(bits));
-                int found = -1;
-                for (const auto& pr : by_tpl[t])
-                    if (pr.first == bits) {
-                        found = pr.second;
-                        break;
-                    }
-                if (found < 0) {
-                    if ((int)gbase.size() >= kTplMax) {
-                        ok = false;
-                        break;
-                    }
-                    found = (int)gbase.size();
-                    gbase.push_back(t);
-                    gdl.push_back(di[i]);
-                    by_tpl[t].push_back({bits, found});
-                }
-                gid[i] = (uint8_t)found;
-            }
-            if (ok) {
-                const int64_t nb = (n_rows + kTplRows - 1) / kTplRows;
-                tblk.assign((size_t)nb, 0);
-                std::vector<int> blist;
-                for (int64_t q = 0; q < nb; ++q) {
-                    bool all = true;
-                    for (int64_t i = q * kTplRows; i < std::min(n_rows, (q + 1) * kTplRows) && all; ++i)
-                        all = gid[i] != kTplNone;
-                    if (all) {
-                        tblk[q] = 1;
-                        blist.push_back((int)q);
-                    }
-                }
-                if (!blist.empty()) {
-                    std::vector<int> gh(gbase.size()), cf(gbase.size(), 0);
-                    std::vector<int> kem(gbase.size(), -1), kep(gbase.size(), -1);
-                    std::vector<double> cvm(gbase.size(), 0.0), cvp(gbase.size(), 0.0);
-                    for (size_t k = 0; k < gbase.size(); ++k) {
-                        const int h = hdrs[gbase[k]];
-                        gh[k] = h;
-                        const int st = h & 0xffff, ln = (h >> 16) & 0xff;
-                        for (int e = st; e < st + ln; ++e) {
-                            if (toff[e] == -1) cvm[k] = tval[e], cf[k] |= 1, kem[k] = e - st;
-                            if (toff[e] == 1) cvp[k] = tval[e], cf[k] |= 2, kep[k] = e - st;
-                        }
-                    }
-                    gs_tcvm.upload(cvm.data(), cvm.size());
-                    gs_tcvp.upload(cvp.data(), cvp.size());
-                    gs_tcf.upload(cf.data(), cf.size());
-                    gs_tkem.upload(kem.data(), kem.size());
-                    gs_tkep.upload(kep.data(), kep.size());
-                    gs_racc.alloc((size_t)n_rows);
-                    gs_tid.upload(gid.data(), gid.size());
-                    gs_thdr.upload(gh.data(), gh.size());
-                    gs_tdl.upload(gdl.data(), gdl.size());
-                    gs_tblocks.upload(blist.data(), blist.size());
-                    if (tpl_mne > 0) {  // uniform stencil: a GS template's mask is its row template's
-                        std::vector<unsigned> tm_(n_tpl), gm(gbase.size());
-                        HIP_CHECK(hipMemcpy(tm_.data(), tpl_mmask.p, sizeof(unsigned) * n_tpl, hipMemcpyDeviceToHost));
-                        for (size_t k = 0; k < gbase.size(); ++k) gm[k] = tm_[gbase[k]];
-                        gs_tmask.upload(gm.data(), gm.size());
-                    }
-                    n_gs_tpl = (int)gbase.size();
-                    n_gs_tblk = (int)blist.size();
-                } else {
-                    tblk.clear();
-                }
-            }
+        gid[i] = (uint8_t)found;
+    }
+    const int64_t nb = (n_rows + kTplRows - 1) / kTplRows;
+    std::vector<char> tblk((size_t)nb, 0);
+    std::vector<int> blist;
+    for (int64_t q = 0; q < nb; ++q) {
+        bool all = true;
+        for (int64_t i = q * kTplRows; i < std::min(n_rows, (q + 1) * kTplRows) && all; ++i)
+            all = gid[i] != kTplNone;
+        if (all) {
+            tblk[q] = 1;
+            blist.push_back((int)q);
         }
     }
+    if (blist.empty()) return {};
+    std::vector<int> gh(gbase.size()), cf(gbase.size(), 0);
+    std::vector<int> kem(gbase.size(), -1), kep(gbase.size(), -1);
+    std::vector<double> cvm(gbase.size(), 0.0), cvp(gbase.size(), 0.0);
+    for (size_t k = 0; k < gbase.size(); ++k) {
+        const int h = T.hdr_host[gbase[k]];
+        gh[k] = h;
+        const int st = h & 0xffff, ln = (h >> 16) & 0xff;
+        for (int e = st; e < st + ln; ++e) {
+            if (T.off_host[e] == -1) cvm[k] = T.val_host[e], cf[k] |= 1, kem[k] = e - st;
+            if (T.off_host[e] == 1) cvp[k] = T.val_host[e], cf[k] |= 2, kep[k] = e - st;
+        }
+    }
+    G.cvm.upload(cvm.data(), cvm.size());
+    G.cvp.upload(cvp.data(), cvp.size());
+    G.cf.upload(cf.data(), cf.size());
+    G.kem.upload(kem.data(), kem.size());
+    G.kep.upload(kep.data(), kep.size());
+    G.racc.alloc((size_t)n_rows);
+    G.id.upload(gid.data(), gid.size());
+    G.hdr.upload(gh.data(), gh.size());
+    G.dl.upload(gdl.data(), gdl.size());
+    G.blocks.upload(blist.data(), blist.size());
+    if (T.master.ne > 0) {  // uniform stencil: a GS template's mask is its row template's
+        std::vector<unsigned> gm(gbase.size());
+        for (size_t k = 0; k < gbase.size(); ++k) gm[k] = T.master.mask_host[gbase[k]];
+        G.mask.upload(gm.data(), gm.size());
+    }
+    G.n = (int)gbase.size();
+    G.n_blk = (int)blist.size();
+    return tblk;
+}
+
+// The rows off the template kernel: chunks packed whole into <= 64-row slabs; interior slabs
+// (no halo column) first, so par_hybrid_gs runs them while the halo is in flight.  Returns the
+// slabs {first row, rows, offset / 64, width} in that order, their count of interior slabs and
+// of sliced-ELL cells.
+static std::vector<int4> gs_pack_slabs(const HostCSR& H, const std::vector<char>& tblk, int64_t first_row,
+                                       int64_t first_col, int64_t n_cols_local, int64_t B, int& n_int,
+                                       int64_t& cells) {
+    const int64_t n_rows = H.nrows();
     auto on_tpl = [&](int64_t r) { return !tblk.empty() && tblk[(size_t)(r / kTplRows)] != 0; };
-    // the other rows: chunks packed whole into <= 64-row slabs; interior slabs (no halo
-    // column) first, so par_hybrid_gs runs them while the halo is in flight
     std::vector<int4> slabs;
     std::vector<char> sbnd;
     for (int64_t r = 0; r < n_rows;) {
@@ -1440,50 +1506,106 @@ void DevMatrix::ensure_gs_blocks(int64_t B) {
         int w = 0;
         char bnd = 0;
         for (int64_t i = r; i < end; ++i) {
-            w = std::max<int>(w, (int)(host.rp[i + 1] - host.rp[i]));
-            for (int64_t k = host.rp[i]; k < host.rp[i + 1] && !bnd; ++k)
-                bnd = host.col[k] < first_col || host.col[k] >= first_col + n_cols_local;
+            w = std::max<int>(w, (int)(H.rp[i + 1] - H.rp[i]));
+            for (int64_t k = H.rp[i]; k < H.rp[i + 1] && !bnd; ++k)
+                bnd = H.col[k] < first_col || H.col[k] >= first_col + n_cols_local;
         }
         slabs.push_back(make_int4((int)r, (int)(end - r), 0, w));
         sbnd.push_back(bnd);
         r = end;
     }
-    {
-        std::vector<int4> ordered;
-        ordered.reserve(slabs.size());
-        for (int pass = 0; pass < 2; ++pass)
-            for (size_t q = 0; q < slabs.size(); ++q)
-                if (sbnd[q] == pass) ordered.push_back(slabs[q]);
-        n_gs_slabs_int = 0;
-        for (char c : sbnd) n_gs_slabs_int += c == 0;
-        slabs.swap(ordered);
-    }
-    int64_t cells = 0;
-    for (int4& sl : slabs) {
+    std::vector<int4> ordered;
+    ordered.reserve(slabs.size());
+    for (int pass = 0; pass < 2; ++pass)
+        for (size_t q = 0; q < slabs.size(); ++q)
+            if (sbnd[q] == pass) ordered.push_back(slabs[q]);
+    n_int = 0;
+    for (char c : sbnd) n_int += c == 0;
+    cells = 0;
+    for (int4& sl : ordered) {
         sl.z = (int)cells;
         cells += (sl.w + 3) & ~3;  // slabs start at multiples of 4 cells (dictionary dwords)
     }
     AMG_CHECK((cells + 4) * 64 < INT_MAX, "hybrid GS: sliced-ELL too large for int32 offsets");
-    gs_slabs.upload(slabs.data(), slabs.size());
-    gs_slabs_host = slabs;
-    gs_cells = cells;
-    gs_ell_built = false;
-    gs_col.reset();
-    gs_val.reset();
-    gs_vid.reset();
-    gs_vtab.reset();
-    gs_ndict = 0;
-    gs_dinv.upload(di.data(), di.size());
-    n_gs_slabs = (int)slabs.size();
-    gs_block = B;
+    return ordered;
+}
+
+// The chain ELL of direction d: the same slabs, only the new-value couplings, in consumption
+// order.  Fills S's arrays of direction d; returns the ELL's cells.
+static int64_t gs_chain_ell(GsFormat::Split& S, int d, const HostCSR& H, const GsChunks& ch,
+                            const std::vector<int4>& slabs) {
+    std::vector<int4> cs = slabs;
+    int64_t cc = 0;
+    for (int4& sl : cs) {
+        int w = 0;
+        for (int l = 0; l < sl.y; ++l) {
+            const int64_t i = sl.x + l;
+            int c = 0;
+            for (int64_t k = H.rp[i]; k < H.rp[i + 1]; ++k) c += ch.is_new(d, i, H.col[k]);
+            w = std::max(w, c);
+        }
+        sl.z = (int)cc;
+        sl.w = w;
+        cc += (w + 3) & ~3;
+    }
+    std::vector<int> ccol((size_t)(cc + 4) * 64, -1);
+    std::vector<double> cval(ccol.size(), 0.0);
+#pragma omp parallel for schedule(dynamic, 64)
+    for (size_t q = 0; q < cs.size(); ++q) {
+        const int4 sl = cs[q];
+        for (int l = 0; l < sl.y; ++l) {
+            const int64_t i = sl.x + l;
+            int c = 0;
+            // consumption order: forward ascending, backward descending column
+            for (int64_t kk = H.rp[i]; kk < H.rp[i + 1]; ++kk) {
+                const int64_t k = d == 0 ? kk : H.rp[i + 1] - 1 - (kk - H.rp[i]);
+                if (ch.is_new(d, i, H.col[k])) {
+                    const size_t at = ((size_t)sl.z + (size_t)c++) * 64 + l;
+                    ccol[at] = (int)(H.col[k] - ch.clo);
+                    cval[at] = H.val[k];
+                }
+            }
+        }
+    }
+    // one chain launch: every slab in the widest slab's width bucket (one launch per
+    // bucket measured slower, g3sub 1560 -> 1360 V-cycles/s: the coarse levels pay
+    // the extra launches, profiles/r4f_g3sub_buckets.txt)
+    int wmax = 0;
+    for (const int4& sl : cs) wmax = std::max(wmax, sl.w);
+    for (int q = 0; q <= kGsChainBuckets; ++q) S.cbucket[d][q] = 0;
+    S.cbucket[d][gs_chain_bucket(wmax) + 1] = (int)cs.size();
+    for (int q = 0; q < kGsChainBuckets; ++q) S.cbucket[d][q + 1] += S.cbucket[d][q];
+    S.cslabs[d].upload(cs.data(), cs.size());
+    S.ccol[d].upload(ccol.data(), ccol.size());
+    S.cval[d].upload(cval.data(), cval.size());
+    S.cmaxw[d] = wmax;
+    return cc;
+}
+
+void DevMatrix::ensure_gs_blocks(int64_t B) {
+    const HostCSR& H = host_image();  // the member `host`, or the CSR a worker builds from
+    AMG_CHECK(square, "hybrid GS needs a square matrix");
+    AMG_CHECK(B >= 1 && B <= 64, "hybrid GS block must be in [1, 64]");
+    if (gs.block == B) return;
+    const BuildKnobs knobs = read_build_knobs();
+    gs = GsFormat{};  // a build for another block size starts from nothing
+    const std::vector<double> di = gs_l1_diagonal(H, first_row, B);
+    std::vector<char> tblk;
+    if (knobs.gs_templates) tblk = gs_templates(gs.tpl, tpl, di, first_row, B);
+    std::vector<int4> slabs = gs_pack_slabs(H, tblk, first_row, first_col, n_cols_local, B, gs.n_slabs_int, gs.cells);
+    const int64_t cells = gs.cells;
+    gs.slabs.upload(slabs.data(), slabs.size());
+    gs.dinv.upload(di.data(), di.size());
+    gs.n_slabs = (int)slabs.size();
+    gs.block = B;
     // bytes per sweep: ELL cells + slab headers + 32 B per ELL row (b, x, dinv, y)
     int64_t ell_rows = 0;
     for (const int4& sl : slabs) ell_rows += sl.y;
-    gs_bytes = (gs_ndict > 0 ? 5 : 12) * 64 * cells + 16 * (int64_t)slabs.size() + 32 * ell_rows;
+    gs.bytes = (gs.ndict > 0 ? 5 : 12) * 64 * cells + 16 * (int64_t)slabs.size() + 32 * ell_rows;
     // template rows: acc kernel 1 B id + b + x (window) + acc out; chain kernel acc + x + id + y
-    if (n_gs_tblk > 0)
-        gs_bytes += 50 * (n_rows - ell_rows) + 16 * (int64_t)n_tpl_ent + 12 * (int64_t)n_gs_tpl;
-    gs_wide = !slabs.empty() && cells >= (int64_t)kGsWide * (int64_t)slabs.size();
+    if (gs.tpl.n_blk > 0)
+        gs.bytes += 50 * (n_rows - ell_rows) + 16 * (int64_t)tpl.n_ent + 12 * (int64_t)gs.tpl.n;
+    gs.wide = !slabs.empty() && cells >= (int64_t)kGsWide * (int64_t)slabs.size();
 
     // Split sweeps: the old-value couplings as a CSR-block pass (KM_GSACC on A
     // without the sweep's in-chunk new-value couplings -- the same entries in the same order,
@@ -1496,102 +1618,27 @@ void DevMatrix::ensure_gs_blocks(int64_t B) {
     // interior blocks run, and the old values across ranks are the Jacobi-across-ranks half of
     // the oracle's rank-cut definition -- results unchanged.  The pass is built collectively,
     // so the ranks agree first: all split or none do.
-    gs_split = false;
-    for (int d = 0; d < 2; ++d) {
-        gs_old[d].reset();
-        gs_cslabs[d].reset();
-        gs_ccol[d].reset();
-        gs_cval[d].reset();
+    bool split = knobs.gs_split && gs.tpl.n_blk == 0 && n_rows > 0 && nnz >= knobs.gs_split_npr * n_rows;
+    if (ctx->host.nranks > 1 && !replicated)
+        for (int64_t v : ctx->host.allgather((int64_t)(split ? 1 : 0))) split = split && v != 0;
+    gs.slabs_host = slabs;
+    if (!split) {
+        ensure_gs_ell();
+        return;
     }
-    gs_acc.reset();
-    {
-        const char* e = std::getenv("AMG_GS_SPLIT_NPR");
-        const int64_t npr = e ? std::atoll(e) : (int64_t)12;
-        const char* off = std::getenv("AMG_GS_SPLIT");
-        const bool allow = !(off && std::atoi(off) == 0);
-        bool split = allow && n_gs_tblk == 0 && n_rows > 0 && nnz >= npr * n_rows;
-        if (ctx->host.nranks > 1 && !replicated)
-            for (int64_t v : ctx->host.allgather((int64_t)(split ? 1 : 0))) split = split && v != 0;
-        if (split) {
-            // in-chunk new-value coupling of row i (local ids): forward cs <= j < i, backward
-            // i < j < ce (hybrid_gs_kernel's [lo, hi))
-            auto chunk = [&](int64_t i, int64_t& cs, int64_t& ce) {
-                const int64_t g = first_row + i;
-                cs = std::max<int64_t>(0, (g / B) * B - first_row);
-                ce = std::min<int64_t>(n_rows, (g / B + 1) * B - first_row);
-            };
-            auto is_new = [&](int d, int64_t i, int64_t gc) {
-                if (gc < clo || gc >= chi) return false;
-                const int64_t j = gc - clo;
-                int64_t cs, ce;
-                chunk(i, cs, ce);
-                return d == 0 ? (j >= cs && j < i) : (j > i && j < ce);
-            };
-            int64_t ccells = 0;
-            gs_split = true;  // (ensure_gs_pass checks it)
-            for (int d = 0; d < 2; ++d) {
-                // the backward pass (post-smoothing) is built now; the forward one on first
-                // use (ensure_gs_pass): a coarse level's forward sweep starts from x = 0 and
-                // skips it (par_hybrid_gs_from_zero)
-                if (d == 1) ensure_gs_pass(1);
-                // the chain ELL: same slabs, only the new-value couplings (CSR order)
-                std::vector<int4> cs = slabs;
-                int64_t cc = 0;
-                for (int4& sl : cs) {
-                    int w = 0;
-                    for (int l = 0; l < sl.y; ++l) {
-                        const int64_t i = sl.x + l;
-                        int c = 0;
-                        for (int64_t k = host.rp[i]; k < host.rp[i + 1]; ++k) c += is_new(d, i, host.col[k]);
-                        w = std::max(w, c);
-                    }
-                    sl.z = (int)cc;
-                    sl.w = w;
-                    cc += (w + 3) & ~3;
-                }
-                std::vector<int> ccol((size_t)(cc + 4) * 64, -1);
-                std::vector<double> cval(ccol.size(), 0.0);
-#pragma omp parallel for schedule(dynamic, 64)
-                for (size_t q = 0; q < cs.size(); ++q) {
-                    const int4 sl = cs[q];
-                    for (int l = 0; l < sl.y; ++l) {
-                        const int64_t i = sl.x + l;
-                        int c = 0;
-                        // consumption order: forward ascending, backward descending column
-                        for (int64_t kk = host.rp[i]; kk < host.rp[i + 1]; ++kk) {
-                            const int64_t k = d == 0 ? kk : host.rp[i + 1] - 1 - (kk - host.rp[i]);
-                            if (is_new(d, i, host.col[k])) {
-                                const size_t at = ((size_t)sl.z + (size_t)c++) * 64 + l;
-                                ccol[at] = (int)(host.col[k] - clo);
-                                cval[at] = host.val[k];
-                            }
-                        }
-                    }
-                }
-                // one chain launch: every slab in the widest slab's width bucket (one launch per
-                // bucket measured slower, g3sub 1560 -> 1360 V-cycles/s: the coarse levels pay
-                // the extra launches, profiles/r4f_g3sub_buckets.txt)
-                int wmax = 0;
-                for (const int4& sl : cs) wmax = std::max(wmax, sl.w);
-                for (int q = 0; q <= kGsChainBuckets; ++q) gs_cbucket[d][q] = 0;
-                gs_cbucket[d][gs_chain_bucket(wmax) + 1] = (int)cs.size();
-                for (int q = 0; q < kGsChainBuckets; ++q) gs_cbucket[d][q + 1] += gs_cbucket[d][q];
-                gs_cslabs[d].upload(cs.data(), cs.size());
-                gs_ccol[d].upload(ccol.data(), ccol.size());
-                gs_cval[d].upload(cval.data(), cval.size());
-                gs_cmaxw[d] = 0;
-                for (const int4& sl : cs) gs_cmaxw[d] = std::max(gs_cmaxw[d], sl.w);
-                if (d == 0) ccells = cc;
-            }
-            gs_acc.alloc((size_t)n_rows);
-            gs_split = true;
-            // bytes per (forward) sweep: the pass (its stored format + b + acc out), then the
-            // chain ELL cells + slab headers + acc, x, dinv in and y out
-            gs_bytes = gs_old[1]->mode_bytes(KM_RESID) + 8 * n_rows + 12 * 64 * ccells +
-                       16 * (int64_t)slabs.size() + 32 * n_rows;
-        }
-    }
-    if (!gs_split) ensure_gs_ell();
+    gs.split.on = true;  // (ensure_gs_pass checks it)
+    // the backward pass (post-smoothing) is built now; the forward one on first use
+    // (ensure_gs_pass): a coarse level's forward sweep starts from x = 0 and skips it
+    // (par_hybrid_gs_from_zero)
+    const GsChunks ch(*this);
+    const int64_t ccells = gs_chain_ell(gs.split, 0, H, ch, slabs);
+    ensure_gs_pass(1);
+    gs_chain_ell(gs.split, 1, H, ch, slabs);
+    gs.split.acc.alloc((size_t)n_rows);
+    // bytes per (forward) sweep: the pass (its stored format + b + acc out), then the
+    // chain ELL cells + slab headers + acc, x, dinv in and y out
+    gs.bytes = gs.split.old[1]->mode_bytes(KM_RESID) + 8 * n_rows + 12 * 64 * ccells +
+               16 * (int64_t)slabs.size() + 32 * n_rows;
 }
 
 int64_t DevMatrix::format_generation = 0;
@@ -1686,7 +1733,7 @@ void par_apply(DevMatrix& A, int mode, const double* x, const double* b, double*
     // partials follow the template kernel's
     const bool tp = A.tpl_on();
     const int c0 = tp ? A.nb_skip : 0;
-    const int poff = tp ? (A.tpl_blocks() - A.nb_skip) * kNormParts : 0;
+    const int poff = tp ? (A.tpl.blocks(A.n_rows) - A.nb_skip) * kNormParts : 0;
     if (tp) launch_tpl(s, mode, norm, A, x, b, y, omega, partial);
     launch_csr_stream(s, mode, norm, A, c0, A.nb_int - c0, x, b, y, omega, partial, poff);
     if (comm) A.halo_wait();
@@ -1707,19 +1754,19 @@ bool par_restrict_j0(DevMatrix& R, const double* r, double* bc, double* x0c, con
 void par_hybrid_gs(DevMatrix& A, const double* x, const double* b, double* y, int64_t block,
                    bool backward, double* partial) {
     A.ensure_gs_blocks(block);
-    if (A.gs_split && !partial) {  // split sweep: the pass exchanges its halo
+    if (A.gs.split.on && !partial) {  // split sweep: the pass exchanges its halo
         A.ensure_gs_pass(backward ? 1 : 0);
-        par_apply(*A.gs_old[backward ? 1 : 0], KM_GSACC, x, b, A.gs_acc.p, 0.0, nullptr);
-        launch_gs_chain(A.ctx->stream, A, x, A.gs_acc.p, y, backward);
+        par_apply(*A.gs.split.old[backward ? 1 : 0], KM_GSACC, x, b, A.gs.split.acc.p, 0.0, nullptr);
+        launch_gs_chain(A.ctx->stream, A, x, A.gs.split.acc.p, y, backward);
         return;
     }
     A.ensure_gs_ell();
     const bool comm = A.halo_begin(x);
     hipStream_t s = A.ctx->stream;
     // template blocks and interior slabs never read the halo: they run while it is in flight
-    launch_hybrid_gs(s, A, x, b, y, backward, partial, 0, A.n_gs_slabs_int, true);
+    launch_hybrid_gs(s, A, x, b, y, backward, partial, 0, A.gs.n_slabs_int, true);
     if (comm) A.halo_wait();
-    launch_hybrid_gs(s, A, x, b, y, backward, partial, A.n_gs_slabs_int, A.n_gs_slabs, false);
+    launch_hybrid_gs(s, A, x, b, y, backward, partial, A.gs.n_slabs_int, A.gs.n_slabs, false);
 }
 
 // Forward sweep from x = 0 (the first pre-smoothing sweep of a coarse level): every old-value
@@ -1728,7 +1775,7 @@ void par_hybrid_gs(DevMatrix& A, const double* x, const double* b, double* y, in
 // halo exchange are skipped and the chain walk starts from acc = b.  Other forms sweep as usual.
 void par_hybrid_gs_from_zero(DevMatrix& A, const double* x0, const double* b, double* y, int64_t block) {
     A.ensure_gs_blocks(block);
-    if (A.gs_split) {
+    if (A.gs.split.on) {
         launch_gs_chain(A.ctx->stream, A, x0, b, y, false);
         return;
     }
