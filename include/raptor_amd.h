@@ -187,6 +187,11 @@ int amg_par_csr_mult_add(amg_matrix A, const double* x, double* y);        /* y 
 int amg_par_csr_residual(amg_matrix A, const double* x, const double* b, double* r);
 int amg_par_csr_jacobi(amg_matrix A, const double* x, const double* b, double* x_out,
                        double omega);
+/* One step k >= 1 of the Chebyshev smoother (the level kernel of AMG_SMOOTH_CHEBYSHEV, DESIGN.md
+ * 3): x_out_i = x_i + (c1 (x_i - x_prev_i) + c2 (1/a_ii) (b - A x)_i).  x_prev may be NULL (zeros)
+ * and x_out may be x_prev (the step then overwrites the iterate before x); x_out must not be x. */
+int amg_par_csr_chebyshev_step(amg_matrix A, const double* x, const double* x_prev, const double* b,
+                               double* x_out, double c1, double c2);
 int amg_par_csr_hybrid_gs(amg_matrix A, const double* x, const double* b, double* x_out,
                           int64_t block);
 /* the backward sweep (rows of each block in descending order; the V-cycle's post-smoother) */
@@ -206,6 +211,8 @@ int amg_par_csr_destroy(amg_matrix A);
 #define AMG_COARSEN_SA 2     /* smoothed aggregation over MIS(2) aggregates              */
 #define AMG_SMOOTH_JACOBI 0
 #define AMG_SMOOTH_HYBRID_GS 1
+#define AMG_SMOOTH_CHEBYSHEV 2  /* Chebyshev polynomial in D^-1 A on [f hi, hi], hi = 1.1 lambda_l
+                                 * (DESIGN.md 3): SpMV-shaped passes only, partition independent */
 #define AMG_INTERP_CLASSICAL 0  /* RS / PMIS: distance-one classical (modified) interpolation  */
 #define AMG_INTERP_EXT_I 1      /* RS / PMIS: distance-two extended+i with P_max truncation    *
                                  * (any number of ranks; PMIS: built on the GPU) */
@@ -235,6 +242,10 @@ typedef struct amg_options {
                                  A_{l+1} = R A_l P with |a_ij| < drop_tol sqrt(|a_ii a_jj|) are
                                  added to the diagonal (row order; row sums kept).  0 = the
                                  Galerkin operator (default).  DESIGN.md 3                  */
+    int32_t cheby_degree;     /* AMG_SMOOTH_CHEBYSHEV: degree of the polynomial = operator passes
+                                 of one smoothing sweep, 1 .. 16.  Default 2                 */
+    double cheby_fraction;    /* AMG_SMOOTH_CHEBYSHEV: the polynomial damps [f hi, hi]; 0 < f < 1.
+                                 Default 0.3.  Both are read (and checked) only under Chebyshev */
 } amg_options;
 
 #define AMG_PRESET_PMIS_JACOBI 0  /* config 2/4: 7-pt Poisson, Jacobi V-cycle            */
@@ -271,6 +282,10 @@ int amg_solver_level_setup_device(amg_solver S, int32_t level, int32_t* out);
  * exceeded the per-wavefront LDS capacity and were built through global scratch; *launches =
  * kernel launches the count pass split the rows into.  l < num_levels - 1. */
 int amg_solver_level_ext_stats(amg_solver S, int32_t level, int64_t* scratch_rows, int64_t* launches);
+/* AMG_SMOOTH_CHEBYSHEV: level l's estimate lambda_l of rho(D^-1 A_l), 10 max-norm power steps
+ * from the seeded vector of seed + l (the same on every partition).  AMG_ERR_INVALID for the
+ * coarsest level or another smoother. */
+int amg_solver_level_eig(amg_solver S, int32_t level, double* lambda);
 /* One V-cycle x <- cycle(x, b) (ParMultilevel::cycle). */
 int amg_solver_cycle(amg_solver S, double* x, const double* b);
 /* ParMultilevel::solve: r0 = ||b-Ax||; up to max_iter cycles until ||r||/r0 < tol.

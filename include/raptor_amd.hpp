@@ -122,6 +122,12 @@ public:
     void jacobi(const double* x, const double* b, double* x_out, double omega = 2.0 / 3.0) const {
         check(amg_par_csr_jacobi(h_, x, b, x_out, omega));
     }
+    // one step k >= 1 of the Chebyshev smoother: x_out = x + (c1 (x - x_prev) + c2 D^-1 (b - A x));
+    // x_prev may be null (zeros) and x_out may be x_prev, but not x
+    void chebyshev_step(const double* x, const double* x_prev, const double* b, double* x_out, double c1,
+                        double c2) const {
+        check(amg_par_csr_chebyshev_step(h_, x, x_prev, b, x_out, c1, c2));
+    }
     void hybrid_gs(const double* x, const double* b, double* x_out, int64_t block = 64, bool backward = false) const {
         check(backward ? amg_par_csr_hybrid_gs_backward(h_, x, b, x_out, block)
                        : amg_par_csr_hybrid_gs(h_, x, b, x_out, block));
@@ -183,6 +189,13 @@ public:
         std::vector<int32_t> s((size_t)level_info(level).n_local);
         check(amg_solver_level_split(h_, level, s.data()));
         return s;
+    }
+    // AMG_SMOOTH_CHEBYSHEV: the level's estimate of rho(D^-1 A_l) (throws for the coarsest level
+    // or another smoother).  opt.cheby_degree / opt.cheby_fraction set the polynomial
+    double level_eig(int level) const {
+        double v = 0.0;
+        check(amg_solver_level_eig(h_, level, &v));
+        return v;
     }
     // true: level's split and P came from the device setup path (not the host fallback)
     bool level_setup_on_device(int level) const {

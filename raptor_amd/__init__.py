@@ -38,6 +38,7 @@ from ._lib import (  # noqa: F401  (re-exported constants)
     AMG_COARSEN_SA,
     AMG_INTERP_CLASSICAL,
     AMG_INTERP_EXT_I,
+    AMG_SMOOTH_CHEBYSHEV,
     AMG_SMOOTH_HYBRID_GS,
     AMG_SMOOTH_JACOBI,
     AMG_STENCIL_5PT,
@@ -456,6 +457,14 @@ class ParCSRMatrix:
         check(lib().amg_par_csr_jacobi(self.h, _ptr(x), _ptr(b), _ptr(x_out), float(omega)))
         return x_out
 
+    def chebyshev_step(self, x, x_prev, b, x_out, c1, c2):
+        """One step k >= 1 of the Chebyshev smoother (the level kernel of smoother="chebyshev"):
+        x_out = x + (c1 (x - x_prev) + c2 D^-1 (b - A x)).  ``x_prev`` may be None (zeros) and
+        ``x_out`` may be ``x_prev``; ``x_out`` must not be ``x``."""
+        check(lib().amg_par_csr_chebyshev_step(self.h, _ptr(x), _ptr(x_prev), _ptr(b), _ptr(x_out),
+                                               float(c1), float(c2)))
+        return x_out
+
     def hybrid_gs(self, x, b, x_out, block=64, backward=False):
         """One hybrid GS sweep (GS inside blocks of `block` rows, Jacobi across blocks and
         ranks); backward=True walks each block's rows in descending order."""
@@ -585,7 +594,9 @@ class ParMultilevel:
     """AMG hierarchy + V-cycle (RAPtor ParMultilevel analogue).
 
     ``coarsen``: "rs" (serial Ruge-Stueben), "pmis", or "sa" (smoothed aggregation over MIS(2)
-    aggregates).  ``smoother``: "jacobi" or "hybrid_gs".  ``interp`` (RS / PMIS): "classical"
+    aggregates).  ``smoother``: "jacobi", "hybrid_gs" or "chebyshev" (a polynomial of degree
+    ``cheby_degree`` in D^-1 A that damps [``cheby_fraction`` hi, hi], hi = 1.1 x the level's
+    eigenvalue estimate; symmetric and partition independent).  ``interp`` (RS / PMIS): "classical"
     (distance one) or "ext+i" (distance two, ``p_max`` entries kept per row; any number of
     ranks, built on the GPU under PMIS).
     ``drop_tol`` > 0: coarse operators lose their off-diagonals below drop_tol sqrt(|a_ii a_jj|),
@@ -593,19 +604,22 @@ class ParMultilevel:
 
     _COARSEN = {"rs": AMG_COARSEN_RS, "pmis": AMG_COARSEN_PMIS, "sa": AMG_COARSEN_SA}
     _INTERP = {"classical": AMG_INTERP_CLASSICAL, "ext+i": AMG_INTERP_EXT_I}
-    _SMOOTH = {"jacobi": AMG_SMOOTH_JACOBI, "hybrid_gs": AMG_SMOOTH_HYBRID_GS}
+    _SMOOTH = {"jacobi": AMG_SMOOTH_JACOBI, "hybrid_gs": AMG_SMOOTH_HYBRID_GS,
+               "chebyshev": AMG_SMOOTH_CHEBYSHEV}
 
     def __init__(self, coarsen="pmis", smoother="jacobi", strong_threshold=None,
                  jacobi_omega=2.0 / 3.0, pre_sweeps=1, post_sweeps=1, max_levels=25,
                  max_coarse=256, gs_block=64, seed=0x5EED, use_graph=None, setup_device=True,
-                 replicate_below=262144, interp="classical", p_max=4, drop_tol=0.0):
+                 replicate_below=262144, interp="classical", p_max=4, drop_tol=0.0,
+                 cheby_degree=2, cheby_fraction=0.3):
         if strong_threshold is None:
             strong_threshold = 0.08 if coarsen == "sa" else 0.25
         self.options = Options(self._COARSEN[coarsen], self._SMOOTH[smoother],
                                float(strong_threshold), float(jacobi_omega), int(pre_sweeps),
                                int(post_sweeps), int(max_levels), int(max_coarse), int(gs_block),
                                int(seed), int(setup_device), int(replicate_below),
-                               self._INTERP[interp], int(p_max), float(drop_tol))
+                               self._INTERP[interp], int(p_max), float(drop_tol),
+                               int(cheby_degree), float(cheby_fraction))
         self.use_graph = use_graph
         self.h = None
         self.A = None
@@ -647,6 +661,13 @@ class ParMultilevel:
         check(lib().amg_solver_level_split(self.h, int(level),
                                            out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
+
+    def level_eig(self, level: int) -> float:
+        """smoother="chebyshev": the level's estimate of rho(D^-1 A_l) (10 max-norm power steps,
+        the same on every partition).  Raises for the coarsest level or another smoother."""
+        v = C.c_double()
+        check(lib().amg_solver_level_eig(self.h, int(level), C.byref(v)))
+        return v.value
 
     def level_setup_on_device(self, level: int) -> int:
         """1 if the level's split and P were built by the device setup path, 0 if the host

@@ -13,7 +13,7 @@ lib_path = os.environ.get("RAPTOR_AMD_LIB") or os.path.join(_HERE, "libraptor_am
 AMG_OK = 0
 AMG_STENCIL_5PT, AMG_STENCIL_7PT, AMG_STENCIL_27PT = 0, 1, 2
 AMG_COARSEN_RS, AMG_COARSEN_PMIS, AMG_COARSEN_SA = 0, 1, 2
-AMG_SMOOTH_JACOBI, AMG_SMOOTH_HYBRID_GS = 0, 1
+AMG_SMOOTH_JACOBI, AMG_SMOOTH_HYBRID_GS, AMG_SMOOTH_CHEBYSHEV = 0, 1, 2
 AMG_INTERP_CLASSICAL, AMG_INTERP_EXT_I = 0, 1
 AMG_PRESET_PMIS_JACOBI, AMG_PRESET_RS_JACOBI, AMG_PRESET_SA_HYBRID_GS = 0, 1, 2
 AMG_REORDER_RCM = 1
@@ -45,6 +45,8 @@ class Options(C.Structure):
         ("interp", C.c_int32),
         ("p_max", C.c_int32),
         ("drop_tol", C.c_double),
+        ("cheby_degree", C.c_int32),
+        ("cheby_fraction", C.c_double),
     ]
 
 
@@ -134,6 +136,7 @@ SIGNATURES = {
     "amg_par_csr_mult_add": (C.c_int, [_vp, _vp, _vp]),
     "amg_par_csr_residual": (C.c_int, [_vp, _vp, _vp, _vp]),
     "amg_par_csr_jacobi": (C.c_int, [_vp, _vp, _vp, _vp, _f64]),
+    "amg_par_csr_chebyshev_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f64, _f64]),
     "amg_par_csr_hybrid_gs": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),
     "amg_par_csr_hybrid_gs_backward": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),
     "amg_par_csr_residual_norm": (C.c_int, [_vp, _vp, _vp, _pf64]),
@@ -145,6 +148,7 @@ SIGNATURES = {
     "amg_solver_level_info": (C.c_int, [_vp, _i32, C.POINTER(LevelInfo)]),
     "amg_solver_level_matrix": (C.c_int, [_vp, _i32, _i32, C.POINTER(_vp)]),
     "amg_solver_level_split": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "amg_solver_level_eig": (C.c_int, [_vp, _i32, C.POINTER(_f64)]),
     "amg_solver_level_setup_device": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
     "amg_solver_level_ext_stats": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
     "amg_solver_cycle": (C.c_int, [_vp, _vp, _vp]),

@@ -467,6 +467,19 @@ int amg_par_csr_jacobi(amg_matrix A, const double* x, const double* b, double* x
     return apply(A, KM_JACOBI, x, b, xo, omega);
 }
 
+int amg_par_csr_chebyshev_step(amg_matrix A, const double* x, const double* xp, const double* b, double* xo,
+                               double c1, double c2) {
+    return guard([&] {
+        AMG_CHECK(A, "null matrix");
+        AMG_CHECK((x && b && xo) || A->m->n_rows == 0, "null vector");
+        AMG_CHECK(x != xo || A->m->n_rows == 0, "the Chebyshev step is out of place: x and x_out must differ");
+        set_device(*A->m->ctx);
+        A->m->ensure_built();
+        release_setup_image(*A->m);
+        par_apply(*A->m, KM_CHEBY, x, b, xo, c2, nullptr, xp, c1);
+    });
+}
+
 int amg_par_csr_hybrid_gs(amg_matrix A, const double* x, const double* b, double* xo, int64_t block) {
     return guard([&] {
         AMG_CHECK(A, "null matrix");
@@ -559,6 +572,8 @@ int amg_options_default(int preset, amg_options* o) {
         o->interp = AMG_INTERP_CLASSICAL;
         o->p_max = 4;
         o->drop_tol = 0.0;
+        o->cheby_degree = 2;
+        o->cheby_fraction = 0.3;
         if (preset == AMG_PRESET_RS_JACOBI) {
             o->coarsen = AMG_COARSEN_RS;
         } else if (preset == AMG_PRESET_SA_HYBRID_GS) {
@@ -658,6 +673,15 @@ int amg_solver_level_ext_stats(amg_solver S, int32_t l, int64_t* scratch_rows, i
         const bool have = (size_t)l < S->s.level_ext_stats.size();
         *scratch_rows = have ? S->s.level_ext_stats[l][0] : 0;
         *launches = have ? S->s.level_ext_stats[l][1] : 0;
+    });
+}
+
+int amg_solver_level_eig(amg_solver S, int32_t l, double* lambda) {
+    return guard([&] {
+        AMG_CHECK(S && lambda, "null argument");
+        AMG_CHECK(S->s.opt.smoother == AMG_SMOOTH_CHEBYSHEV, "eigenvalue estimates exist under the Chebyshev smoother");
+        AMG_CHECK(l >= 0 && l + 1 < (int32_t)S->s.levels.size(), "level has no smoother (the coarsest level is solved)");
+        *lambda = S->s.cheby[l].lambda;
     });
 }
 

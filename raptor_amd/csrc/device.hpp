@@ -493,7 +493,11 @@ struct DevMatrix {
 // KM_GSACC (square, no norm): y_i = b_i - sum_j a_ij x_j, subtracted one product at a time in
 // CSR order (acc = b; acc -= a_ij x_j) -- the old-value half of an l1 hybrid GS sweep
 //  on an operator without the sweep's in-chunk couplings
-enum KernelMode { KM_SPMV = 0, KM_SPMV_ADD = 1, KM_RESID = 2, KM_JACOBI = 3, KM_GSACC = 4 };
+// KM_CHEBY (square, no norm): one step k >= 1 of the Chebyshev smoother,
+// y_i = x_i + (c1 (x_i - xprev_i) + c2 (dinv_i (b_i - sum_j a_ij x_j))) -- KM_JACOBI plus the
+// per-row operand xprev (null: zeros).  y may alias xprev (a row's xprev is read only by the lane
+// that writes the row); the launchers take c2 as `omega`
+enum KernelMode { KM_SPMV = 0, KM_SPMV_ADD = 1, KM_RESID = 2, KM_JACOBI = 3, KM_GSACC = 4, KM_CHEBY = 5 };
 
 // launchers (kernels.hip); all enqueue on s
 // KernelVariant bits in effect for A (DevMatrix::default_variant and the bits of what was
@@ -503,10 +507,12 @@ int kernel_variant(const DevMatrix& A);
 void launch_csr_stream(hipStream_t s, int mode, bool norm, const DevMatrix& A, int first_block,
                        int n_blocks, const double* x, const double* b, double* y, double omega,
                        double* partial, int part_off = 0,
-                       double* y2 = nullptr, const double* d2 = nullptr);
+                       double* y2 = nullptr, const double* d2 = nullptr, const double* xprev = nullptr,
+                       double c1 = 0.0);
 // template rows of A (all of them, one launch); partials at [0, tpl.blocks(n_rows) * kNormParts)
 void launch_tpl(hipStream_t s, int mode, bool norm, const DevMatrix& A, const double* x,
-                const double* b, double* y, double omega, double* partial);
+                const double* b, double* y, double omega, double* partial, const double* xprev = nullptr,
+                double c1 = 0.0);
 // hybrid GS sweep over slabs [s0, s1) of the sliced-ELL copy, plus (tpl) the template blocks;
 // partials: slab q at q, template block list entry t, wave w at gs.n_slabs + 4 t + w
 void launch_hybrid_gs(hipStream_t s, const DevMatrix& A, const double* x, const double* b,
@@ -517,7 +523,8 @@ void launch_gs_chain(hipStream_t s, const DevMatrix& A, const double* x, const d
                      double* y, bool backward);
 // plain CSR (AMG_FORMAT_CSR): all rows, one launch; partials at [0, plain_blocks() * kNormParts)
 void launch_csr_plain(hipStream_t s, int mode, bool norm, const DevMatrix& A, const double* x,
-                      const double* b, double* y, double omega, double* partial);
+                      const double* b, double* y, double omega, double* partial, const double* xprev = nullptr,
+                      double c1 = 0.0);
 // dst = src (16-byte nontemporal copy kernel; the bench's STREAM-copy ceiling)
 void launch_copy(hipStream_t s, int64_t n, const double* src, double* dst);
 // one read pass over src (16-byte loads), per-wave partial sums into part[read_partials(n)]
@@ -550,8 +557,9 @@ void launch_uniform(hipStream_t s, int64_t n, int64_t first_gid, uint64_t seed, 
 void launch_zero(hipStream_t s, int64_t n, double* y);
 
 // ParCSRMatrix operations with halo exchange + interior/boundary overlap
+// KM_CHEBY: omega = c2, xprev (null: zeros; y may alias it, y must not alias x) and c1
 void par_apply(DevMatrix& A, int mode, const double* x, const double* b, double* y, double omega,
-               double* partial_or_null);
+               double* partial_or_null, const double* xprev = nullptr, double c1 = 0.0);
 // partial (forward only): per-slab sums of (b - A x)^2 for a fused residual norm
 void par_hybrid_gs(DevMatrix& A, const double* x, const double* b, double* y, int64_t block,
                    bool backward = false, double* partial = nullptr);
@@ -652,8 +660,23 @@ struct Solver {
     // x0_in_t: level l's first pre-sweep from x = 0 already sits in levels[l].t (fused into
     // the restriction above, par_restrict_j0)
     void cycle_rec(size_t l, double* x, const double* b, bool x_zero, bool with_norm, bool x0_in_t = false);
+    // x0_in_t (Chebyshev): step 0 of this application already sits in tmp
     void smooth(size_t l, double*& x, const double* b, double*& tmp, bool x_zero, bool with_norm,
-                bool post = false);
+                bool post = false, bool x0_in_t = false);
+    // Chebyshev smoother: per non-coarsest level the estimate lambda_l of
+    // rho(D^-1 A_l) and the coefficients of the degree-m polynomial on [f hi, hi], hi = 1.1 lambda_l
+    // (c1[k], c2[k] for step k >= 1; entry 0 unused).  Launch arguments of the cycle's kernels
+    struct Cheby {
+        double lambda = 0.0, w0 = 0.0;
+        std::vector<double> c1, c2;
+    };
+    std::vector<Cheby> cheby;
+    void setup_cheby();
+    bool jacobi_like() const { return opt.smoother == AMG_SMOOTH_JACOBI || opt.smoother == AMG_SMOOTH_CHEBYSHEV; }
+    // omega of the Jacobi-shaped first step of level l's smoother
+    double omega0(size_t l) const { return opt.smoother == AMG_SMOOTH_CHEBYSHEV ? cheby[l].w0 : opt.jacobi_omega; }
+    // operator passes of one smoothing application (Chebyshev: its degree)
+    int sweep_steps() const { return opt.smoother == AMG_SMOOTH_CHEBYSHEV ? opt.cheby_degree : 1; }
     void ensure_hist(int32_t n);
     bool can_fuse_norm() const;
     // ParMultilevel::solve; hist_host gets it+1 norms

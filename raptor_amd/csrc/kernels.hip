@@ -106,7 +106,24 @@ struct CsrArgs {
     const uint16_t* col16;  // gather operators: 16-bit column codes (C16 kernels), with
     const int4* gband;      // the block's 4 band bases: col = base[code >> 14] + (code & 0x3fff)
     int nblk;               // blocks of this launch
+    // KM_CHEBY (one Chebyshev step): the iterate before x (null: zeros; may alias
+    // y -- a row's entry is read only by the lane that writes the row) and c1; c2 is `omega`
+    const double* xprev;
+    double c1;
 };
+
+// KM_CHEBY takes Jacobi's operand routes (x[r] from the x tile or the template window, 1/a_ii
+// from a value table, the template table or the dinv stream)
+template <int MODE>
+constexpr bool kJacobiOperands = MODE == KM_JACOBI || MODE == KM_CHEBY;
+
+// the Chebyshev step's epilogue: x' = x + (c1 (x - xprev) + c2 (dinv t)), t = b - sum
+__device__ __forceinline__ double cheby_update(double x, double xprev, double dinv, double t, double c1, double c2) {
+    const double u = x - xprev;
+    const double v = dinv * t;
+    const double w = (c1 * u) + (c2 * v);
+    return x + w;
+}
 
 // the fused second output of a restriction (CsrArgs::y2): jacobi_zero_kernel's expression;
 // d = dinv[r], loaded with the row operands (a load after the sum cost a memory round trip
@@ -130,6 +147,7 @@ __device__ __forceinline__ double epilogue(const CsrArgs& a, int r, double s, do
     const double t = a.b[r] - s;
     *res = t;
     if (MODE == KM_RESID) return t;
+    if (MODE == KM_CHEBY) return cheby_update(a.x[r], a.xprev ? a.xprev[r] : 0.0, a.dinv[r], t, a.c1, a.omega);
     // Jacobi: x + omega * (dinv * (b - s))
     return a.x[r] + a.omega * (a.dinv[r] * t);
 }
@@ -344,18 +362,21 @@ __device__ __forceinline__ double block_main(const CsrArgs& a, int bid, double* 
     const int rr = own ? r : r0;
     const int e1 = a.rend[rr];
     rends[tid] = e1;
-    const bool px_tile = TILE && MODE == KM_JACOBI && h1.x >= 0;       // block-uniform
-    const bool pd_tab = VIB && MODE == KM_JACOBI && (h1.y & kHdrDvi) != 0;  // block-uniform
-    double pb = 0.0, pd = 0.0, px = 0.0;
+    const bool px_tile = TILE && kJacobiOperands<MODE> && h1.x >= 0;       // block-uniform
+    const bool pd_tab = VIB && kJacobiOperands<MODE> && (h1.y & kHdrDvi) != 0;  // block-uniform
+    double pb = 0.0, pd = 0.0, px = 0.0, pp = 0.0;
     int dv = 0;
     if (MODE == KM_SPMV_ADD) px = a.y[rr];
     if (MODE == KM_SPMV && a.y2) pd = a.dinv[rr];  // store_y2
-    if (MODE == KM_RESID || MODE == KM_JACOBI || MODE == KM_GSACC) pb = a.b[rr];
-    if (MODE == KM_JACOBI) {
+    if (MODE == KM_RESID || kJacobiOperands<MODE> || MODE == KM_GSACC) pb = a.b[rr];
+    if (kJacobiOperands<MODE>) {
         if (pd_tab) dv = a.dvi[rr];
         else pd = a.dinv[rr];
         if (!px_tile) px = a.x[rr];
     }
+    // Chebyshev: the row's own entry of the iterate before x (kernel-uniform null test); y may
+    // alias it, so a lane without a row discards what it re-read of row r0
+    if (MODE == KM_CHEBY && a.xprev) pp = a.xprev[rr];
     // the scheduling barrier keeps every earlier load issued before the first x load waits
     // for its line / column id
     __builtin_amdgcn_sched_barrier(0);
@@ -456,7 +477,8 @@ __device__ __forceinline__ double block_main(const CsrArgs& a, int bid, double* 
     } else {
         const double t = pb - s;
         if (NORM) sq = own ? t * t : 0.0;
-        out = MODE == KM_RESID ? t : px + a.omega * (pd * t);
+        if (MODE == KM_CHEBY) out = cheby_update(px, pp, pd, t, a.c1, a.omega);
+        else out = MODE == KM_RESID ? t : px + a.omega * (pd * t);
     }
     if (own) {
         a.y[r] = out;
@@ -601,6 +623,8 @@ struct PlainArgs {
     double* y;
     double omega;
     double* partial;
+    const double* xprev;  // KM_CHEBY (CsrArgs): the iterate before x (null: zeros; may alias y)
+    double c1;            // and c1; c2 is `omega`
 };
 
 __device__ __forceinline__ double plain_x(const PlainArgs& a, int c) {
@@ -617,13 +641,14 @@ __global__ __launch_bounds__(kTPB, 8) void csr_plain_kernel(PlainArgs a) {
     const int rr = own ? r : r1 - 1;
     const int k0 = a.rp[r0], k1 = a.rp[r1];  // workgroup-uniform (scalar loads)
     const int rs = a.rp[rr], re = a.rp[rr + 1];
-    double pb = 0.0, pd = 0.0, px = 0.0;
+    double pb = 0.0, pd = 0.0, px = 0.0, pp = 0.0;
     if (MODE == KM_SPMV_ADD) px = a.y[rr];
-    if (MODE == KM_RESID || MODE == KM_JACOBI) pb = a.b[rr];
-    if (MODE == KM_JACOBI) {
+    if (MODE == KM_RESID || kJacobiOperands<MODE>) pb = a.b[rr];
+    if (kJacobiOperands<MODE>) {
         pd = a.dinv[rr];
         px = a.x[rr];
     }
+    if (MODE == KM_CHEBY && a.xprev) pp = a.xprev[rr];
     const int plast = max(k1 - 1, 0) & ~1;  // last pair holding a real entry (padding after)
     double s = 0.0;
     for (int base = k0 & ~1; base < k1; base += kCAP) {
@@ -652,7 +677,8 @@ __global__ __launch_bounds__(kTPB, 8) void csr_plain_kernel(PlainArgs a) {
     } else {
         const double t = pb - s;
         if (NORM) sq = own ? t * t : 0.0;
-        out = MODE == KM_RESID ? t : px + a.omega * (pd * t);
+        if (MODE == KM_CHEBY) out = cheby_update(px, pp, pd, t, a.c1, a.omega);
+        else out = MODE == KM_RESID ? t : px + a.omega * (pd * t);
     }
     if (own) a.y[r] = out;
     if (NORM) {
@@ -745,6 +771,8 @@ struct TplArgs {
     double mpd;
     int mslot[kTplMasterMax];
     double mval[kTplMasterMax];
+    const double* xprev;  // KM_CHEBY (CsrArgs): the iterate before x (null: zeros; may alias y)
+    double c1;            // and c1; c2 is `omega`
 };
 
 // dynamic LDS: window | values | 1/a_ii (Jacobi only) | entry slots or offsets | headers.
@@ -791,7 +819,7 @@ __device__ __forceinline__ TplLds tpl_lds_layout(const TplArgs& a) {
     L.win = tpl_lds;
     L.val = L.win + a.win;
     L.pd = L.val + a.nent;
-    L.off = (int*)(L.pd + (MODE == KM_JACOBI ? kTplMax + 1 : 0));
+    L.off = (int*)(L.pd + (kJacobiOperands<MODE> ? kTplMax + 1 : 0));
     L.hdr = L.off + a.nent;
     return L;
 }
@@ -812,7 +840,7 @@ __device__ __forceinline__ void tpl_stage_table(const TplArgs& a, const TplLds& 
     }
     if (tid < a.ntpl) {
         L.hdr[tid] = a.hdr[tid];  // MNE > 0: the template's entry mask
-        if (MODE == KM_JACOBI && MNE == 0) L.pd[tid] = a.pd[tid];
+        if (kJacobiOperands<MODE> && MNE == 0) L.pd[tid] = a.pd[tid];
     }
     // length 0, no diagonal / no master entry
     if (tid == kTplNone) L.hdr[kTplNone] = MNE > 0 ? 0 : (int)(255u << 24);
@@ -864,14 +892,16 @@ struct TplFetch {
         }
     }
 
-    // b / y: needed only by the epilogue
+    // b / y: needed only by the epilogue (KM_CHEBY: py holds the row's xprev, read by the lane
+    // that writes the row, so y may alias xprev)
     __device__ __forceinline__ void issue_operands(const TplArgs& a) {
 #pragma unroll
         for (int j = 0; j < R; ++j) {
             pb[j] = 0.0;
             py[j] = 0.0;
-            if (MODE == KM_RESID || MODE == KM_JACOBI) pb[j] = a.b[rr[j]];
+            if (MODE == KM_RESID || kJacobiOperands<MODE>) pb[j] = a.b[rr[j]];
             if (MODE == KM_SPMV_ADD) py[j] = a.y[rr[j]];
+            if (MODE == KM_CHEBY && a.xprev) py[j] = a.xprev[rr[j]];
         }
     }
 
@@ -940,7 +970,7 @@ __device__ __forceinline__ double tpl_rows(const TplArgs& a, const TplLds& L, __
         s[j] = 0.0;
         xr[j] = 0.0;
         // Jacobi needs x[r]; a template without a diagonal entry reads it here (rare)
-        if (MODE == KM_JACOBI && dk[j] == 255 && id[j] != kTplNone) xr[j] = a.x[rr[j]];
+        if (kJacobiOperands<MODE> && dk[j] == 255 && id[j] != kTplNone) xr[j] = a.x[rr[j]];
     }
     if constexpr (NPL > 0 && AMG_TPL_BATCH > 0) {
         // window, batched: both rows of the lane advance together, B entries per batch; the
@@ -966,7 +996,7 @@ __device__ __forceinline__ double tpl_rows(const TplArgs& a, const TplLds& L, __
                     const int k = k0 + u;
                     const double p = L.val[min(st[j] + k, elast)] * xv[u][j];
                     s[j] = k < ln[j] ? s[j] + p : s[j];
-                    if (MODE == KM_JACOBI) xr[j] = k == dk[j] ? xv[u][j] : xr[j];
+                    if (kJacobiOperands<MODE>) xr[j] = k == dk[j] ? xv[u][j] : xr[j];
                 }
         }
     } else if constexpr (NPL > 0) {
@@ -996,7 +1026,7 @@ __device__ __forceinline__ double tpl_rows(const TplArgs& a, const TplLds& L, __
         // per entry)
 #pragma unroll
         for (int j = 0; j < R; ++j)
-            if (MODE == KM_JACOBI && dk[j] != 255) xr[j] = L.win[L.off[st[j] + dk[j]] + kTPB * j + tid];
+            if (kJacobiOperands<MODE> && dk[j] != 255) xr[j] = L.win[L.off[st[j] + dk[j]] + kTPB * j + tid];
     } else {
         // global x: both rows of the lane advance together, C entries per batch, every load
         // of a batch issued before its first product
@@ -1020,7 +1050,7 @@ __device__ __forceinline__ double tpl_rows(const TplArgs& a, const TplLds& L, __
                     const int k = k0 + u;
                     const double p = L.val[min(st[j] + k, elast)] * xv[u][j];
                     s[j] = k < ln[j] ? s[j] + p : s[j];
-                    if (MODE == KM_JACOBI) xr[j] = k == dk[j] ? xv[u][j] : xr[j];
+                    if (kJacobiOperands<MODE>) xr[j] = k == dk[j] ? xv[u][j] : xr[j];
                 }
         }
     }
@@ -1036,7 +1066,8 @@ __device__ __forceinline__ double tpl_rows(const TplArgs& a, const TplLds& L, __
         } else {
             const double t = pb[j] - s[j];
             if (NORM) sq += own ? t * t : 0.0;
-            out = MODE == KM_RESID ? t : xr[j] + a.omega * (L.pd[MODE == KM_JACOBI ? id[j] : 0] * t);
+            if (MODE == KM_CHEBY) out = cheby_update(xr[j], py[j], L.pd[id[j]], t, a.c1, a.omega);
+            else out = MODE == KM_RESID ? t : xr[j] + a.omega * (L.pd[MODE == KM_JACOBI ? id[j] : 0] * t);
         }
         if (own) a.y[r0 + kTPB * j + tid] = out;
     }
@@ -1199,7 +1230,8 @@ __device__ __forceinline__ double tpl_rows_master(const TplArgs& a, const TplLds
             const double t = pb[j] - s[j];
             if (NORM) sq += own ? t * t : 0.0;
             // Jacobi: x_r from the window at the master's diagonal slot (every template has it)
-            out = MODE == KM_RESID ? t : wr[j][a.mslot[a.mdiag]] + a.omega * (a.mpd * t);
+            if (MODE == KM_CHEBY) out = cheby_update(wr[j][a.mslot[a.mdiag]], py[j], a.mpd, t, a.c1, a.omega);
+            else out = MODE == KM_RESID ? t : wr[j][a.mslot[a.mdiag]] + a.omega * (a.mpd * t);
         }
         if (own) a.y[r0 + tpl_lrow<true>(tid, j)] = out;
     }
@@ -1238,6 +1270,23 @@ constexpr int tpl_waves(int npl) { return npl > 8 ? 4 : 6; }
 #define AMG_MARCH_NORM_WAVES 7
 #endif
 constexpr int tpl_march_waves(int npl, bool norm) { return npl == 8 ? (norm ? AMG_MARCH_NORM_WAVES : 7) : tpl_waves(npl); }
+// KM_CHEBY holds two more doubles per lane (the rows' xprev) across the rows than Jacobi does:
+// its persistent and marching forms are compiled for the most waves per SIMD at which they take
+// no scratch (the uniform 27-entry stencil's forms keep the prefetched window and 27 products'
+// operands live: 3 or 4 waves); DESIGN.md 4.6 lists every form beside its Jacobi sibling
+constexpr int tpl_cheby_waves(bool march, int npl, int mne) {
+    if (mne == 27) return npl == 4 || (march && npl == 8) ? 4 : 3;
+    if (npl == 8) return march && mne == 0 ? 6 : 5;
+    return tpl_waves(npl);
+}
+template <int MODE>
+constexpr int tpl_persist_bound(int npl, int mne) {
+    return MODE == KM_CHEBY ? tpl_cheby_waves(false, npl, mne) : tpl_waves(npl);
+}
+template <int MODE>
+constexpr int tpl_march_bound(int npl, int mne, bool norm) {
+    return MODE == KM_CHEBY ? tpl_cheby_waves(true, npl, mne) : tpl_march_waves(npl, norm);
+}
 
 // one workgroup per block of kTplRows rows
 template <int MODE, bool NORM, int NPL, int MNE = 0>
@@ -1261,7 +1310,7 @@ __global__ __launch_bounds__(kTPB, 6) void tpl_kernel(TplArgs a) {
 // fetched into registers while the current block is computed from LDS (double buffering
 // through registers), so the load latency overlaps the arithmetic.
 template <int MODE, bool NORM, int NPL, int MNE = 0>
-__global__ __launch_bounds__(kTPB, tpl_waves(NPL)) void tpl_persist_kernel(TplArgs a, int nblk) {
+__global__ __launch_bounds__(kTPB, tpl_persist_bound<MODE>(NPL, MNE)) void tpl_persist_kernel(TplArgs a, int nblk) {
     static_assert(NPL > 0, "window path only");
     const TplLds L = tpl_lds_layout<MODE>(a);
     const __amdgpu_buffer_rsrc_t xrs = tpl_xrs(a);
@@ -1300,7 +1349,7 @@ __global__ __launch_bounds__(kTPB, tpl_waves(NPL)) void tpl_persist_kernel(TplAr
 // only the rest is loaded -- 1024 instead of 2048 doubles per 7-pt block.  The next block's
 // loaded slots and row ids are prefetched into registers during the current block.
 template <int MODE, bool NORM, int NPL, int MNE = 0>
-__global__ __launch_bounds__(kTPB, tpl_march_waves(NPL, NORM)) void tpl_march_kernel(TplArgs a, int nblk, int S, int nchunk) {
+__global__ __launch_bounds__(kTPB, tpl_march_bound<MODE>(NPL, MNE, NORM)) void tpl_march_kernel(TplArgs a, int nblk, int S, int nchunk) {
     static_assert(NPL > 0 && NPL % 2 == 0, "window path, slot pairs");
     constexpr int NP = NPL / 2;  // slot pairs per lane (16-byte loads and LDS copies)
     const TplLds L = tpl_lds_layout<MODE>(a);
@@ -2095,22 +2144,25 @@ static void launch_tpl_window(hipStream_t s, const TplArgs& a, int g, size_t lds
         hipLaunchKernelGGL((tpl_kernel<M, N, P, K>), dim3(g), dim3(kTPB), lds, s, a);
         return;
     }
-    thread_local int cus = 0, occ = 0;
-    thread_local size_t occ_lds = 0;
-    if (cus == 0) {
-        int dev = 0;
-        HIP_CHECK(hipGetDevice(&dev));
-        HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    // (KM_CHEBY: the persistent form of the larger windows, never launched, is not instantiated)
+    if constexpr (M != KM_CHEBY || P <= 8) {
+        thread_local int cus = 0, occ = 0;
+        thread_local size_t occ_lds = 0;
+        if (cus == 0) {
+            int dev = 0;
+            HIP_CHECK(hipGetDevice(&dev));
+            HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        }
+        if (occ_lds != lds) {
+            HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tpl_persist_kernel<M, N, P, K>, kTPB, lds));
+            occ_lds = lds;
+        }
+        const int gp = std::min(g, cus * occ) / 8 * 8;
+        if (gp >= 8 && g > gp)
+            hipLaunchKernelGGL((tpl_persist_kernel<M, N, P, K>), dim3(gp), dim3(kTPB), lds, s, a, g);
+        else
+            hipLaunchKernelGGL((tpl_kernel<M, N, P, K>), dim3(g), dim3(kTPB), lds, s, a);
     }
-    if (occ_lds != lds) {
-        HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, tpl_persist_kernel<M, N, P, K>, kTPB, lds));
-        occ_lds = lds;
-    }
-    const int gp = std::min(g, cus * occ) / 8 * 8;
-    if (gp >= 8 && g > gp)
-        hipLaunchKernelGGL((tpl_persist_kernel<M, N, P, K>), dim3(gp), dim3(kTPB), lds, s, a, g);
-    else
-        hipLaunchKernelGGL((tpl_kernel<M, N, P, K>), dim3(g), dim3(kTPB), lds, s, a);
 }
 
 // AMG_TPL_MARCH_CHUNKS caps the chains per column (tests: longer chains, so the LDS reuse
@@ -2168,7 +2220,7 @@ static void tpl_window_args(TplArgs& a, const TplFormat& T, bool win, int mne, c
 }
 
 void launch_tpl(hipStream_t s, int mode, bool norm, const DevMatrix& A, const double* x,
-                const double* b, double* y, double omega, double* partial) {
+                const double* b, double* y, double omega, double* partial, const double* xprev, double c1) {
     const int g = A.tpl.blocks(A.n_rows);
     if (g <= 0) return;
     AMG_ASSERT(A.square && A.tpl.n > 0 && A.tpl.n <= kTplMax && A.tpl.n_ent <= kTplEntries);
@@ -2187,12 +2239,14 @@ void launch_tpl(hipStream_t s, int mode, bool norm, const DevMatrix& A, const do
     a.y = y;
     a.omega = omega;
     a.partial = partial;
+    a.xprev = xprev;
+    a.c1 = c1;
     // uniform stencil (KV_MASTER): entry masks instead of the template tables
     const int mne = win && (kernel_variant(A) & KV_MASTER) ? A.tpl.master.ne : 0;
     tpl_window_args(a, A.tpl, win, mne, A.tpl.master.mask);
     const int npl = tpl_lanes(a.win);
     AMG_ASSERT(a.win <= npl * kTPB && a.win <= kTplWin);
-    const size_t lds = tpl_lds_bytes(a.win, a.nent, mode == KM_JACOBI);
+    const size_t lds = tpl_lds_bytes(a.win, a.nent, mode == KM_JACOBI || mode == KM_CHEBY);
     const bool march = win && A.tpl.march_s > 0 && (kernel_variant(A) & KV_MARCH);
     if (march) a.wsrc = A.tpl.wsrc.p;
 #define AMG_T3(M, N, P, K)                                                     \
@@ -2226,6 +2280,10 @@ void launch_tpl(hipStream_t s, int mode, bool norm, const DevMatrix& A, const do
         case KM_JACOBI:
             if (norm) AMG_T(KM_JACOBI, true);
             else AMG_T(KM_JACOBI, false);
+            break;
+        case KM_CHEBY:
+            AMG_CHECK(!norm, "Chebyshev step: no fused norm");
+            AMG_T(KM_CHEBY, false);
             break;
         default: throw Error(AMG_ERR_INTERNAL, "bad kernel mode");
     }
@@ -2265,14 +2323,15 @@ static void launch_block(hipStream_t s, dim3 g, const CsrArgs& a, int first_bloc
 
 void launch_csr_stream(hipStream_t s, int mode, bool norm, const DevMatrix& A, int first_block,
                        int n_blocks, const double* x, const double* b, double* y, double omega,
-                       double* partial, int part_off, double* y2, const double* d2) {
+                       double* partial, int part_off, double* y2, const double* d2, const double* xprev,
+                       double c1) {
     if (n_blocks <= 0) return;
     const int ncl = (int)A.n_cols_local, nh = (int)A.n_halo();
     AMG_ASSERT(!y2 || (mode == KM_SPMV && d2));
     CsrArgs a{A.hdr.p, A.tile_fixed.p, A.lcol.p, A.vidx.p, A.vtab.p, A.rend.p, A.dvi.p,
               A.rp.p, A.col.p, A.val.p,
               x, A.halo.p, ncl, nh, (ncl + A.line_w - 1) / A.line_w, (ncl >= 2 && nh != 1) ? 1 : 0, A.tiled ? 0 : 1,
-              b, y2 ? d2 : A.dinv.p, y, omega, partial, part_off, y2, nullptr, A.gband.p, n_blocks};
+              b, y2 ? d2 : A.dinv.p, y, omega, partial, part_off, y2, nullptr, A.gband.p, n_blocks, xprev, c1};
     const dim3 g(n_blocks);
     const int var = kernel_variant(A);
     if (var & KV_C16) a.col16 = A.col16.p;
@@ -2319,6 +2378,10 @@ void launch_csr_stream(hipStream_t s, int mode, bool norm, const DevMatrix& A, i
             AMG_CHECK(!norm && A.square, "GS acc pass: square operator, no norm");
             AMG_L(KM_GSACC, false);
             break;
+        case KM_CHEBY:
+            AMG_CHECK(!norm && A.square, "Chebyshev step: square operator, no norm");
+            AMG_L(KM_CHEBY, false);
+            break;
         default: throw Error(AMG_ERR_INTERNAL, "bad kernel mode");
     }
 #if AMG_CSR_PHASES
@@ -2343,12 +2406,13 @@ void launch_csr_stream(hipStream_t s, int mode, bool norm, const DevMatrix& A, i
 }
 
 void launch_csr_plain(hipStream_t s, int mode, bool norm, const DevMatrix& A, const double* x,
-                      const double* b, double* y, double omega, double* partial) {
+                      const double* b, double* y, double omega, double* partial, const double* xprev,
+                      double c1) {
     const int g = A.plain_blocks();
     if (g <= 0) return;
     AMG_ASSERT(A.pcol.p != nullptr && A.pval.p != nullptr);
     PlainArgs a{A.rp.p, A.pcol.p, A.pval.p, x, A.halo.p, (int)A.n_cols_local, (int)A.n_rows,
-                b, A.dinv.p, y, omega, partial};
+                b, A.dinv.p, y, omega, partial, xprev, c1};
 #define AMG_PL(M, N) hipLaunchKernelGGL((csr_plain_kernel<M, N>), dim3(g), dim3(kTPB), 0, s, a)
     switch (mode) {
         case KM_SPMV: AMG_PL(KM_SPMV, false); break;
@@ -2360,6 +2424,10 @@ void launch_csr_plain(hipStream_t s, int mode, bool norm, const DevMatrix& A, co
         case KM_JACOBI:
             if (norm) AMG_PL(KM_JACOBI, true);
             else AMG_PL(KM_JACOBI, false);
+            break;
+        case KM_CHEBY:
+            AMG_CHECK(!norm, "Chebyshev step: no fused norm");
+            AMG_PL(KM_CHEBY, false);
             break;
         default: throw Error(AMG_ERR_INTERNAL, "bad kernel mode");
     }

@@ -6,6 +6,7 @@
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <exception>
 #include <mutex>
 #include <thread>
@@ -209,7 +210,12 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
     AMG_CHECK(A.square, "AMG setup needs a square matrix");
     AMG_CHECK(o.pre_sweeps >= 0 && o.post_sweeps >= 0, "negative sweep count");
     AMG_CHECK(o.max_levels >= 1, "max_levels must be >= 1");
-    AMG_CHECK(o.smoother == AMG_SMOOTH_JACOBI || o.smoother == AMG_SMOOTH_HYBRID_GS, "bad smoother");
+    AMG_CHECK(o.smoother == AMG_SMOOTH_JACOBI || o.smoother == AMG_SMOOTH_HYBRID_GS ||
+                  o.smoother == AMG_SMOOTH_CHEBYSHEV, "bad smoother");
+    if (o.smoother == AMG_SMOOTH_CHEBYSHEV) {  // read only here: other callers may leave them zero
+        AMG_CHECK(o.cheby_degree >= 1 && o.cheby_degree <= 16, "cheby_degree must be 1 .. 16");
+        AMG_CHECK(o.cheby_fraction > 0.0 && o.cheby_fraction < 1.0, "cheby_fraction must lie in (0, 1)");
+    }
     ctx = A.ctx;
     opt = o;
     A0 = &A;
@@ -481,6 +487,114 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
     // multi-rank cycles: loopback ranks meet at host barriers, which a graph cannot replay;
     // RCCL ranks capture whole cycles where the runtime is the one capture was validated on
     use_graph = comm.nranks == 1 || (ctx->transport == TR_RCCL && rccl_graph_allowed());
+    cheby.clear();
+    if (opt.smoother == AMG_SMOOTH_CHEBYSHEV) {
+        setup_cheby();
+        tm.lap("Chebyshev eigenvalue estimates");
+    }
+}
+
+namespace {
+constexpr int kChebyEigIters = 10;  // power steps of lambda_l (SA's rho: DESIGN.md 3)
+
+// the largest |v_i|: non-negative doubles order like their bit patterns, so an integer atomicMax
+// is exact in any order
+__device__ __forceinline__ void eig_max_abs(unsigned long long* m, double v) {
+    atomicMax(m, (unsigned long long)__double_as_longlong(fabs(v)));
+}
+
+__global__ __launch_bounds__(kTPB) void eig_max_kernel(int n, const double* x, unsigned long long* m) {
+    const int i = blockIdx.x * kTPB + threadIdx.x;
+    if (i < n) eig_max_abs(m, x[i]);
+}
+
+__global__ __launch_bounds__(kTPB) void eig_scale_kernel(int n, const double* y, double lam, double* x) {
+    const int i = blockIdx.x * kTPB + threadIdx.x;
+    if (i < n) x[i] = y[i] / lam;
+}
+
+// y_i = (A x)_i / a_ii (the division by the diagonal itself) and max |y_i|
+__global__ __launch_bounds__(kTPB) void eig_div_max_kernel(int n, const double* d, double* y, unsigned long long* m) {
+    const int i = blockIdx.x * kTPB + threadIdx.x;
+    if (i >= n) return;
+    const double v = y[i] / d[i];
+    y[i] = v;
+    eig_max_abs(m, v);
+}
+}  // namespace
+
+// lambda_l = rho(D^-1 A_l) of every level but the coarsest by the power iteration DESIGN.md 3
+// defines for SA's rho, on A_l itself: x = u / max|u|, u the seeded uniform vector of the global
+// ids (seed + l); 10 times y = (A x) / a_ii, lambda = max|y| (exact in any order, so the same on
+// every partition), x = y / lambda; stop at lambda = 0.  Then the coefficients, on the host in
+// the order the definition writes them.
+void Solver::setup_cheby() {
+    const HostComm& comm = ctx->host;
+    hipStream_t s = ctx->stream;
+    cheby.assign(levels.size(), Cheby{});
+    DevBuf<unsigned long long> mx;
+    mx.alloc(1);
+    for (size_t l = 0; l + 1 < levels.size(); ++l) {
+        DevMatrix& A = Amat(l);
+        A.ensure_built();
+        const int n = (int)A.n_rows;
+        const int g = (n + kTPB - 1) / kTPB;
+        const bool dist = comm.nranks > 1 && !A.replicated;  // a replicated level is whole here
+        // a_ii of the local rows from the host image (global column ids)
+        const HostCSR& H = A.host_image();
+        std::vector<double> dh((size_t)std::max(n, 1), 0.0);
+#pragma omp parallel for schedule(static)
+        for (int i = 0; i < n; ++i)
+            for (int64_t k = H.rp[i]; k < H.rp[i + 1]; ++k)
+                if (H.col[k] == A.first_row + i) dh[i] = H.val[k];
+        DevBuf<double> d;
+        d.upload(dh.data(), dh.size());
+        double* x = levels[l].r.p;  // the level's work vectors: free until the first cycle
+        double* y = levels[l].t.p;
+        auto global_max = [&]() {
+            unsigned long long bits = 0;
+            HIP_CHECK(hipMemcpyAsync(&bits, mx.p, sizeof(bits), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            double m;
+            std::memcpy(&m, &bits, sizeof(m));
+            return dist ? comm.allreduce_max(m) : m;
+        };
+        launch_uniform(s, n, A.first_row, opt.seed + (uint64_t)l, x);
+        HIP_CHECK(hipMemsetAsync(mx.p, 0, sizeof(unsigned long long), s));
+        if (n) hipLaunchKernelGGL(eig_max_kernel, dim3(g), dim3(kTPB), 0, s, n, x, mx.p);
+        const double m0 = global_max();
+        if (m0 > 0.0 && n) hipLaunchKernelGGL(eig_scale_kernel, dim3(g), dim3(kTPB), 0, s, n, x, m0, x);
+        double lam = 0.0;
+        for (int it = 0; it < kChebyEigIters; ++it) {
+            par_apply(A, KM_SPMV, x, nullptr, y, 0.0, nullptr);
+            HIP_CHECK(hipMemsetAsync(mx.p, 0, sizeof(unsigned long long), s));
+            if (n) hipLaunchKernelGGL(eig_div_max_kernel, dim3(g), dim3(kTPB), 0, s, n, d.p, y, mx.p);
+            HIP_CHECK(hipGetLastError());
+            lam = global_max();
+            if (lam == 0.0) break;
+            if (n) hipLaunchKernelGGL(eig_scale_kernel, dim3(g), dim3(kTPB), 0, s, n, y, lam, x);
+        }
+        HIP_CHECK(hipStreamSynchronize(s));  // d is freed here
+        Cheby& c = cheby[l];
+        const int m = opt.cheby_degree;
+        c.lambda = lam;
+        c.c1.assign((size_t)m, 0.0);
+        c.c2.assign((size_t)m, 0.0);
+        if (lam == 0.0) continue;  // every coefficient 0.0
+        const double hi = 1.1 * lam;
+        const double lo = opt.cheby_fraction * hi;
+        const double theta = 0.5 * (hi + lo);
+        const double delta = 0.5 * (hi - lo);
+        const double sigma = theta / delta;
+        c.w0 = 1.0 / theta;
+        double rho = 1.0 / sigma;
+        for (int k = 1; k < m; ++k) {
+            const double rk = 1.0 / (2.0 * sigma - rho);
+            c.c1[k] = rk * rho;
+            c.c2[k] = (2.0 * rk) / delta;
+            rho = rk;
+        }
+    }
 }
 
 // Whole-cycle capture with RCCL groups inside: on HIP 7.0.51831 + RCCL 2.26.6
@@ -514,8 +628,37 @@ void Solver::ensure_hist(int32_t n) {
 // Hybrid GS sweeps forward before the coarse correction and backward after it (post):
 // the V-cycle is then a symmetric operator, as CG requires (oracle smooth()).
 void Solver::smooth(size_t l, double*& x, const double* b, double*& tmp, bool x_zero,
-                    bool with_norm, bool post) {
+                    bool with_norm, bool post, bool x0_in_t) {
     DevMatrix& A = CA(l);
+    if (opt.smoother == AMG_SMOOTH_CHEBYSHEV) {
+        // one application of the degree-m polynomial: step 0 is a Jacobi step with omega = w0 on
+        // Jacobi's paths; step k >= 1 writes x_{k+1} over x_{k-1} (y aliases xprev), so the two
+        // buffers keep alternating.  After a step 0 from zero x_{k-1} is zeros: no operand
+        const Cheby& c = cheby[l];
+        bool prev_zero = x_zero;
+        if (x0_in_t) {  // fused into the restriction above (par_restrict_j0)
+            AMG_ASSERT(x_zero && !with_norm);
+        } else if (with_norm) {
+            AMG_ASSERT(!x_zero);
+            par_apply(A, KM_JACOBI, x, b, tmp, c.w0, sink.partial);
+            norm_finish(A, sink);
+        } else if (x_zero) {
+            launch_jacobi_zero(ctx->stream, A.n_rows, b, A.dinv.p, tmp, c.w0);
+        } else {
+            par_apply(A, KM_JACOBI, x, b, tmp, c.w0, nullptr);
+        }
+        std::swap(x, tmp);
+        if (!x0_in_t)
+            mark(l, post ? "post-smooth step 0" : with_norm ? "pre-smooth step 0 + norm"
+                                              : x_zero ? "pre-smooth step 0 from 0" : "pre-smooth step 0");
+        for (int k = 1; k < opt.cheby_degree; ++k) {
+            par_apply(A, KM_CHEBY, x, b, tmp, c.c2[k], nullptr, prev_zero ? nullptr : tmp, c.c1[k]);
+            std::swap(x, tmp);
+            prev_zero = false;
+            mark(l, post ? "post-smooth step" : "pre-smooth step");
+        }
+        return;
+    }
     if (with_norm && opt.smoother == AMG_SMOOTH_HYBRID_GS) {
         // forward GS sweep that also leaves the partials of ||b - A x|| (old x)
         AMG_ASSERT(!x_zero && !post);
@@ -777,7 +920,8 @@ void Solver::cycle_rec(size_t l, double* x, const double* b, bool x_zero, bool w
     double* tmp = L.t.p;
     bool zero = x_zero;
     for (int k = 0; k < opt.pre_sweeps; ++k) {
-        if (k == 0 && x0_in_t) std::swap(cur, tmp);  // the sweep from zero is in tmp already
+        if (opt.smoother == AMG_SMOOTH_CHEBYSHEV) smooth(l, cur, b, tmp, zero, with_norm && k == 0, false, k == 0 && x0_in_t);
+        else if (k == 0 && x0_in_t) std::swap(cur, tmp);  // the sweep from zero is in tmp already
         else smooth(l, cur, b, tmp, zero, with_norm && k == 0);
         zero = false;
     }
@@ -805,8 +949,9 @@ void Solver::cycle_rec(size_t l, double* x, const double* b, bool x_zero, bool w
     } else {
         // Jacobi: the coarse level's first sweep from x = 0 (omega dinv b) rides along with
         // the restriction that produces b (one pass over b and a launch fewer per level)
-        const bool j0 = opt.smoother == AMG_SMOOTH_JACOBI && opt.pre_sweeps >= 1 && l + 2 < levels.size() &&
-                        par_restrict_j0(CR(l), L.r.p, C.b.p, C.t.p, CA(l + 1).dinv.p, opt.jacobi_omega);
+        // (Chebyshev: its step 0, omega = the next level's w0)
+        const bool j0 = jacobi_like() && opt.pre_sweeps >= 1 && l + 2 < levels.size() &&
+                        par_restrict_j0(CR(l), L.r.p, C.b.p, C.t.p, CA(l + 1).dinv.p, omega0(l + 1));
         if (!j0) par_apply(CR(l), KM_SPMV, L.r.p, nullptr, C.b.p, 0.0, nullptr);
         mark(l, j0 ? "restrict + next pre-smooth from 0" : "restrict");
         cycle_rec(l + 1, C.x.p, C.b.p, true, false, j0);
@@ -821,8 +966,7 @@ void Solver::cycle_rec(size_t l, double* x, const double* b, bool x_zero, bool w
 }
 
 bool Solver::can_fuse_norm() const {
-    return (opt.smoother == AMG_SMOOTH_JACOBI || opt.smoother == AMG_SMOOTH_HYBRID_GS) &&
-           opt.pre_sweeps >= 1 && levels.size() >= 2;
+    return (jacobi_like() || opt.smoother == AMG_SMOOTH_HYBRID_GS) && opt.pre_sweeps >= 1 && levels.size() >= 2;
 }
 
 // An exec is destroyed only once the stream has drained: a replay enqueued without a host
@@ -1143,21 +1287,24 @@ int64_t Solver::bytes_per_cycle(size_t l) const {
     if (l + 1 == levels.size()) return 8 * coarse_n * n + 8 * coarse_n + 8 * n;
     const int64_t base = 12 * A.nnz + 4 * (n + 1);
     const int64_t jac = base + 32 * n;
+    // Chebyshev: step 0 costs what a Jacobi sweep costs there, each later step + xprev
+    const int64_t later = (sweep_steps() - 1) * (base + 40 * n);
     int64_t b = 0;
     bool zero = l > 0;
     int64_t sweeps = 0;
     for (int k = 0; k < opt.pre_sweeps; ++k, ++sweeps) {
-        if (zero && opt.smoother == AMG_SMOOTH_JACOBI) b += 24 * n;
+        if (zero && jacobi_like()) b += 24 * n;
         else b += jac + (zero ? 8 * n : 0);
+        b += later;
         zero = false;
     }
     if (zero) b += 8 * n;
     b += base + 24 * n;                                   // residual
     b += spmv_bytes(me.CR(l));                            // restriction
     b += spmv_bytes(me.CP(l)) + 8 * n;                    // interpolation (reads x)
-    b += opt.post_sweeps * jac;
+    b += opt.post_sweeps * (jac + later);
     sweeps += opt.post_sweeps;
-    if (sweeps % 2 == 1) b += 16 * n;                     // copy back
+    if (sweeps * sweep_steps() % 2 == 1) b += 16 * n;     // copy back
     return b;
 }
 
@@ -1174,6 +1321,7 @@ int64_t Solver::stored_bytes_per_cycle(size_t l) const {
     if (l + 1 == levels.size()) return 8 * coarse_n * n + 8 * coarse_n + 8 * n;
     const bool gs = opt.smoother == AMG_SMOOTH_HYBRID_GS;
     const int64_t sweep = gs ? A.gs.bytes : A.mode_bytes(KM_JACOBI);
+    const int64_t later = (sweep_steps() - 1) * A.mode_bytes(KM_CHEBY);  // Chebyshev steps k >= 1
     int64_t b = 0;
     bool zero = l > 0;
     int64_t sweeps = 0;
@@ -1186,15 +1334,16 @@ int64_t Solver::stored_bytes_per_cycle(size_t l) const {
     for (int k = 0; k < opt.pre_sweeps; ++k, ++sweeps) {
         if (zero && !gs) b += (j0 ? 16 : 24) * n;  // omega * dinv * b
         else b += (zero ? sweep0 : sweep) + (zero ? 8 * n : 0);  // (zero fill of x first)
+        b += later;
         zero = false;
     }
     if (zero) b += 8 * n;
     b += A.mode_bytes(KM_RESID);
     b += me.CR(l).mode_bytes(KM_SPMV);
     b += me.CP(l).mode_bytes(KM_SPMV_ADD);
-    b += opt.post_sweeps * sweep;
+    b += opt.post_sweeps * (sweep + later);
     sweeps += opt.post_sweeps;
-    if (sweeps % 2 == 1) b += 16 * n;  // copy back
+    if (sweeps * sweep_steps() % 2 == 1) b += 16 * n;  // copy back
     return b;
 }
 

@@ -1647,13 +1647,14 @@ int64_t DevMatrix::mode_bytes(int mode) const {
     const int64_t n = n_rows;
     if (format == AMG_FORMAT_CSR) {  // residual + 8 n (b), Jacobi + 16 n (b, dinv)
         const int64_t base = csr_plain_bytes();
-        return base + (mode == KM_JACOBI ? 16 * n : mode == KM_SPMV ? 0 : 8 * n);
+        return base + (mode == KM_CHEBY ? 24 * n : mode == KM_JACOBI ? 16 * n : mode == KM_SPMV ? 0 : 8 * n);
     }
     const bool tpl = tpl_on();
     int64_t b = tpl ? spmv_fmt_bytes : csr_fmt_bytes;
     if (mode != KM_SPMV) b += 8 * n;  // b, or y for y += A x
     // template rows take 1/a_ii and x[r] from LDS; CSR-kernel rows stream them
-    if (mode == KM_JACOBI) b += tpl ? jac_extra_csr : jac_extra_all;
+    if (mode == KM_JACOBI || mode == KM_CHEBY) b += tpl ? jac_extra_csr : jac_extra_all;
+    if (mode == KM_CHEBY) b += 8 * n;  // Jacobi + xprev
     return b;
 }
 
@@ -1719,14 +1720,15 @@ bool DevMatrix::halo_begin(const double* x) {
 void DevMatrix::halo_wait() { HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->ev_halo, 0)); }
 
 void par_apply(DevMatrix& A, int mode, const double* x, const double* b, double* y, double omega,
-               double* partial) {
-    if (mode == KM_JACOBI || mode == KM_RESID) AMG_CHECK(A.square, "Jacobi/residual need a square matrix");
+               double* partial, const double* xprev, double c1) {
+    if (mode == KM_JACOBI || mode == KM_RESID || mode == KM_CHEBY)
+        AMG_CHECK(A.square, "Jacobi/residual need a square matrix");
     const bool comm = A.halo_begin(x);
     hipStream_t s = A.ctx->stream;
     const bool norm = partial != nullptr;
     if (A.format == AMG_FORMAT_CSR) {  // plain CSR: one launch over every row, after the halo
         if (comm) A.halo_wait();
-        launch_csr_plain(s, mode, norm, A, x, b, y, omega, partial);
+        launch_csr_plain(s, mode, norm, A, x, b, y, omega, partial, xprev, c1);
         return;
     }
     // template rows never touch the halo: they run with the interior blocks; the CSR kernel's
@@ -1734,10 +1736,10 @@ void par_apply(DevMatrix& A, int mode, const double* x, const double* b, double*
     const bool tp = A.tpl_on();
     const int c0 = tp ? A.nb_skip : 0;
     const int poff = tp ? (A.tpl.blocks(A.n_rows) - A.nb_skip) * kNormParts : 0;
-    if (tp) launch_tpl(s, mode, norm, A, x, b, y, omega, partial);
-    launch_csr_stream(s, mode, norm, A, c0, A.nb_int - c0, x, b, y, omega, partial, poff);
+    if (tp) launch_tpl(s, mode, norm, A, x, b, y, omega, partial, xprev, c1);
+    launch_csr_stream(s, mode, norm, A, c0, A.nb_int - c0, x, b, y, omega, partial, poff, nullptr, nullptr, xprev, c1);
     if (comm) A.halo_wait();
-    launch_csr_stream(s, mode, norm, A, A.nb_int, A.nb_bnd, x, b, y, omega, partial, poff);
+    launch_csr_stream(s, mode, norm, A, A.nb_int, A.nb_bnd, x, b, y, omega, partial, poff, nullptr, nullptr, xprev, c1);
 }
 
 bool par_restrict_j0(DevMatrix& R, const double* r, double* bc, double* x0c, const double* dinvc,
