@@ -179,9 +179,27 @@ int amg_par_csr_format_digest(amg_matrix A, uint64_t* digest);
 /* Host copy of the local rows (global column ids). */
 int amg_par_csr_export(amg_matrix A, int64_t* row_ptr, int64_t* col_global, double* val);
 
-/* ParCSRMatrix::mult and the level kernels (rows a2-a5).  Device pointers, local length.
- * Each call performs the RCCL halo exchange of x it needs, overlapped with the interior
- * rows.                                                                                  */
+/* Vectors.  Every vector argument of the calls below (and of amg_solver_cycle / _solve / _pcg /
+ * _cycle_timeline) is an fp64 device pointer of the rank-local length -- x: n_local_cols
+ * doubles, every other vector: n_local_rows -- aligned to 8 bytes.  (16 bytes are required by
+ * amg_vector_copy / amg_vector_read only.)  A call reads and writes nothing outside those
+ * ranges.  Each entry point checks the following on the half-open byte ranges before it does
+ * any work and returns AMG_ERR_INVALID otherwise:
+ *  - null: a vector the call reads or writes is non-null unless its length is 0; x_prev of the
+ *    Chebyshev step alone may be NULL (zeros);
+ *  - output against x: the output (y, r, x_out) overlaps no part of x, in all seven level
+ *    kernels: they are out of place (rows read x entries other rows' lanes write);
+ *  - exact aliases that are allowed (the same pointer; bit-identical to the out-of-place call --
+ *    each row's b / x_prev entry is read by the lane that then writes the row):
+ *      r == b in residual;  x_out == b in jacobi and chebyshev_step;  x_out == x_prev in
+ *      chebyshev_step;  x_prev == x and b == x (inputs only);  mult_add's y is in-out;
+ *  - rejected: an output that overlaps b or x_prev without being the same pointer; for both
+ *    hybrid GS calls an output that overlaps b at all (their sweeps read b in more than one
+ *    pass);
+ *  - solver calls: x (in-out) and b do not overlap.
+ *
+ * ParCSRMatrix::mult and the level kernels (rows a2-a5).  Each call performs the RCCL halo
+ * exchange of x it needs, overlapped with the interior rows.                              */
 int amg_par_csr_mult(amg_matrix A, const double* x, double* y);            /* y = A x       */
 int amg_par_csr_mult_add(amg_matrix A, const double* x, double* y);        /* y = y + A x   */
 int amg_par_csr_residual(amg_matrix A, const double* x, const double* b, double* r);

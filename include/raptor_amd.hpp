@@ -115,7 +115,11 @@ public:
     int64_t global_rows() const { return info().n_global_rows; }
     void set_format(int32_t format) { check(amg_par_csr_set_format(h_, format)); }
 
-    // ParCSRMatrix::mult and the level kernels (device pointers, local length)
+    // ParCSRMatrix::mult and the level kernels.  Vectors (raptor_amd.h, "Vectors"): fp64 device
+    // pointers of the rank-local length, 8-byte aligned, non-null unless empty.  The output must
+    // not overlap x at all; r == b (residual), x_out == b (jacobi, chebyshev_step) and
+    // x_out == x_prev (chebyshev_step) are allowed as the same pointer, any other overlap of an
+    // output with b / x_prev is refused, and hybrid_gs refuses every overlap of x_out with b.
     void mult(const double* x, double* y) const { check(amg_par_csr_mult(h_, x, y)); }
     void mult_add(const double* x, double* y) const { check(amg_par_csr_mult_add(h_, x, y)); }
     void residual(const double* x, const double* b, double* r) const { check(amg_par_csr_residual(h_, x, b, r)); }

@@ -441,33 +441,44 @@ class ParCSRMatrix:
         check(lib().amg_par_csr_format_digest(self.h, C.byref(d)))
         return d.value
 
+    # Vectors (include/raptor_amd.h, "Vectors"): contiguous float64 device vectors of the local
+    # length -- a view such as buf[1:n + 1] is fine, 8-byte alignment is all the level kernels
+    # need.  The output must not overlap x at all; r is b (residual), x_out is b (jacobi,
+    # chebyshev_step) and x_out is x_prev (chebyshev_step) are allowed as the very same vector and
+    # give the out-of-place bits; any other overlap of an output with b / x_prev, and any overlap
+    # of a hybrid GS output with b, raises AmgError before anything is launched.
     def mult(self, x, y):
+        """y = A x.  ``y`` must not overlap ``x``."""
         check(lib().amg_par_csr_mult(self.h, _ptr(x), _ptr(y)))
         return y
 
     def mult_add(self, x, y):
+        """y = y + A x (``y`` is in-out and must not overlap ``x``)."""
         check(lib().amg_par_csr_mult_add(self.h, _ptr(x), _ptr(y)))
         return y
 
     def residual(self, x, b, r):
+        """r = b - A x.  ``r`` may be ``b`` itself; it must not overlap ``x``."""
         check(lib().amg_par_csr_residual(self.h, _ptr(x), _ptr(b), _ptr(r)))
         return r
 
     def jacobi(self, x, b, x_out, omega=2.0 / 3.0):
+        """x_out = x + omega D^-1 (b - A x).  ``x_out`` may be ``b`` itself; it must not overlap ``x``."""
         check(lib().amg_par_csr_jacobi(self.h, _ptr(x), _ptr(b), _ptr(x_out), float(omega)))
         return x_out
 
     def chebyshev_step(self, x, x_prev, b, x_out, c1, c2):
         """One step k >= 1 of the Chebyshev smoother (the level kernel of smoother="chebyshev"):
         x_out = x + (c1 (x - x_prev) + c2 D^-1 (b - A x)).  ``x_prev`` may be None (zeros) and
-        ``x_out`` may be ``x_prev``; ``x_out`` must not be ``x``."""
+        ``x_out`` may be ``x_prev`` or ``b`` (the very same vector); ``x_out`` must not overlap ``x``."""
         check(lib().amg_par_csr_chebyshev_step(self.h, _ptr(x), _ptr(x_prev), _ptr(b), _ptr(x_out),
                                                float(c1), float(c2)))
         return x_out
 
     def hybrid_gs(self, x, b, x_out, block=64, backward=False):
         """One hybrid GS sweep (GS inside blocks of `block` rows, Jacobi across blocks and
-        ranks); backward=True walks each block's rows in descending order."""
+        ranks); backward=True walks each block's rows in descending order.  ``x_out`` must overlap
+        neither ``x`` nor ``b``."""
         fn = lib().amg_par_csr_hybrid_gs_backward if backward else lib().amg_par_csr_hybrid_gs
         check(fn(self.h, _ptr(x), _ptr(b), _ptr(x_out), int(block)))
         return x_out
@@ -718,6 +729,7 @@ class ParMultilevel:
         return sum(self.level_info(l)["bytes_per_cycle_local"] for l in range(self.num_levels))
 
     def cycle(self, x, b):
+        """One V-cycle on ``x`` (in place).  ``x`` and ``b`` (here and in solve / pcg) must not overlap."""
         check(lib().amg_solver_cycle(self.h, _ptr(x), _ptr(b)))
         return x
 

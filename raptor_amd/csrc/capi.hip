@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <numeric>
 
 #include "device.hpp"
@@ -445,10 +446,49 @@ static void release_setup_image(DevMatrix& M) {
     if (M.setup_csr) M.setup_csr.reset();
 }
 
-static int apply(amg_matrix A, int mode, const double* x, const double* b, double* y, double w) {
+// The vector contract of include/raptor_amd.h ("Vectors"), checked on half-open byte ranges at
+// the top of every entry point that takes vectors, before any HIP call: operands the call
+// touches are non-null (unless their length is 0) and 8-byte aligned, the output overlaps no
+// kNoOverlap operand at all, and a kSameOk operand only as the same pointer.
+enum { kNoOverlap = 0, kSameOk = 1, kNullable = 2 };
+struct VecArg {
+    const char* name;
+    const double* p;
+    int64_t n;
+    int rule;
+};
+
+static bool vec_overlaps(const double* a, int64_t na, const double* b, int64_t nb) {
+    if (!a || !b || na <= 0 || nb <= 0) return false;
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + 8 * (uintptr_t)nb && b0 < a0 + 8 * (uintptr_t)na;
+}
+
+static void check_vectors(const char* call, const VecArg& out, std::initializer_list<VecArg> ins) {
+    auto operand = [&](const VecArg& v) {
+        AMG_CHECK(v.p || v.n <= 0 || (v.rule & kNullable), std::string(call) + ": null vector " + v.name);
+        AMG_CHECK(((uintptr_t)v.p & 7) == 0, std::string(call) + ": vector " + v.name + " is not 8-byte aligned");
+    };
+    if (out.name) operand(out);
+    for (const VecArg& v : ins) {
+        operand(v);
+        if (!out.name || !vec_overlaps(out.p, out.n, v.p, v.n)) continue;
+        AMG_CHECK((v.rule & kSameOk) && v.p == out.p,
+                  std::string(call) + ": " + out.name + " overlaps " + v.name +
+                      ((v.rule & kSameOk) ? " without being the same vector" : " (the call is out of place)"));
+    }
+}
+
+// call / yname: the entry point and its output as include/raptor_amd.h names them (messages)
+static int apply(amg_matrix A, int mode, const char* call, const char* yname, const double* x,
+                 const double* b, double* y, double w) {
     return guard([&] {
         AMG_CHECK(A, "null matrix");
-        AMG_CHECK((x || A->m->n_cols_local == 0) && (y || A->m->n_rows == 0), "null vector");
+        const int64_t nr = A->m->n_rows, nc = A->m->n_cols_local;
+        if (mode == KM_RESID || mode == KM_JACOBI)
+            check_vectors(call, {yname, y, nr, 0}, {{"x", x, nc, kNoOverlap}, {"b", b, nr, kSameOk}});
+        else
+            check_vectors(call, {yname, y, nr, 0}, {{"x", x, nc, kNoOverlap}});
         set_device(*A->m->ctx);
         A->m->ensure_built();
         release_setup_image(*A->m);
@@ -456,23 +496,27 @@ static int apply(amg_matrix A, int mode, const double* x, const double* b, doubl
     });
 }
 
-int amg_par_csr_mult(amg_matrix A, const double* x, double* y) { return apply(A, KM_SPMV, x, nullptr, y, 0.0); }
+int amg_par_csr_mult(amg_matrix A, const double* x, double* y) {
+    return apply(A, KM_SPMV, "mult", "y", x, nullptr, y, 0.0);
+}
 int amg_par_csr_mult_add(amg_matrix A, const double* x, double* y) {
-    return apply(A, KM_SPMV_ADD, x, nullptr, y, 0.0);
+    return apply(A, KM_SPMV_ADD, "mult_add", "y", x, nullptr, y, 0.0);
 }
 int amg_par_csr_residual(amg_matrix A, const double* x, const double* b, double* r) {
-    return apply(A, KM_RESID, x, b, r, 0.0);
+    return apply(A, KM_RESID, "residual", "r", x, b, r, 0.0);
 }
 int amg_par_csr_jacobi(amg_matrix A, const double* x, const double* b, double* xo, double omega) {
-    return apply(A, KM_JACOBI, x, b, xo, omega);
+    return apply(A, KM_JACOBI, "jacobi", "x_out", x, b, xo, omega);
 }
 
 int amg_par_csr_chebyshev_step(amg_matrix A, const double* x, const double* xp, const double* b, double* xo,
                                double c1, double c2) {
     return guard([&] {
         AMG_CHECK(A, "null matrix");
-        AMG_CHECK((x && b && xo) || A->m->n_rows == 0, "null vector");
-        AMG_CHECK(x != xo || A->m->n_rows == 0, "the Chebyshev step is out of place: x and x_out must differ");
+        const int64_t nr = A->m->n_rows;
+        check_vectors("chebyshev_step", {"x_out", xo, nr, 0},
+                      {{"x", x, A->m->n_cols_local, kNoOverlap}, {"b", b, nr, kSameOk},
+                       {"x_prev", xp, nr, kSameOk | kNullable}});
         set_device(*A->m->ctx);
         A->m->ensure_built();
         release_setup_image(*A->m);
@@ -483,7 +527,8 @@ int amg_par_csr_chebyshev_step(amg_matrix A, const double* x, const double* xp, 
 int amg_par_csr_hybrid_gs(amg_matrix A, const double* x, const double* b, double* xo, int64_t block) {
     return guard([&] {
         AMG_CHECK(A, "null matrix");
-        AMG_CHECK(x != xo, "hybrid GS is out of place: x and x_out must differ");
+        check_vectors("hybrid_gs", {"x_out", xo, A->m->n_rows, 0},
+                      {{"x", x, A->m->n_cols_local, kNoOverlap}, {"b", b, A->m->n_rows, kNoOverlap}});
         set_device(*A->m->ctx);
         A->m->ensure_built();
         release_setup_image(*A->m);
@@ -495,7 +540,8 @@ int amg_par_csr_hybrid_gs_backward(amg_matrix A, const double* x, const double* 
                                    int64_t block) {
     return guard([&] {
         AMG_CHECK(A, "null matrix");
-        AMG_CHECK(x != xo, "hybrid GS is out of place: x and x_out must differ");
+        check_vectors("hybrid_gs_backward", {"x_out", xo, A->m->n_rows, 0},
+                      {{"x", x, A->m->n_cols_local, kNoOverlap}, {"b", b, A->m->n_rows, kNoOverlap}});
         set_device(*A->m->ctx);
         A->m->ensure_built();
         release_setup_image(*A->m);
@@ -521,6 +567,8 @@ int amg_par_csr_matmat(amg_matrix A, amg_matrix B, amg_matrix* out) {
 int amg_par_csr_residual_norm(amg_matrix A, const double* x, const double* b, double* out) {
     return guard([&] {
         AMG_CHECK(A && out, "null argument");
+        check_vectors("residual_norm", {nullptr, nullptr, 0, 0},
+                      {{"x", x, A->m->n_cols_local, 0}, {"b", b, A->m->n_rows, 0}});
         Context& c = *A->m->ctx;
         set_device(c);
         A->m->ensure_built();
@@ -685,9 +733,16 @@ int amg_solver_level_eig(amg_solver S, int32_t l, double* lambda) {
     });
 }
 
+// the solver calls: x (in-out) and b are non-null and do not overlap
+static void check_solver_vectors(const char* call, amg_solver S, const double* x, const double* b) {
+    const int64_t n = S->s.Amat(0).n_rows;
+    check_vectors(call, {"x", x, n, 0}, {{"b", b, n, kNoOverlap}});
+}
+
 int amg_solver_cycle(amg_solver S, double* x, const double* b) {
     return guard([&] {
         AMG_CHECK(S, "null solver");
+        check_solver_vectors("cycle", S, x, b);
         set_device(*S->s.ctx);
         S->s.cycle(x, b);
     });
@@ -698,6 +753,7 @@ int amg_solver_solve(amg_solver S, double* x, const double* b, int32_t max_iter,
     return guard([&] {
         AMG_CHECK(S && hist && iters, "null argument");
         AMG_CHECK(max_iter >= 0, "max_iter must be >= 0");
+        check_solver_vectors("solve", S, x, b);
         set_device(*S->s.ctx);
         const int32_t it = S->s.solve(x, b, max_iter, tol, hist);
         *iters = it;
@@ -708,6 +764,7 @@ int amg_solver_pcg(amg_solver S, double* x, const double* b, int32_t max_iter, d
                    double* hist, int32_t* iters) {
     return guard([&] {
         AMG_CHECK(S && hist && iters, "null argument");
+        check_solver_vectors("pcg", S, x, b);
         set_device(*S->s.ctx);
         *iters = S->s.pcg(x, b, max_iter, tol, hist);
     });
@@ -733,6 +790,7 @@ int amg_solver_cycle_timeline(amg_solver S, double* x, const double* b, int32_t 
     return guard([&] {
         AMG_CHECK(S && us && labels && n_ops && in_graph, "null argument");
         AMG_CHECK(n_max >= 0 && label_bytes >= 2, "bad buffer sizes");
+        check_solver_vectors("cycle_timeline", S, x, b);
         set_device(*S->s.ctx);
         std::vector<std::string> lab;
         std::vector<double> t;
