@@ -159,6 +159,9 @@ typedef struct amg_matrix_info {
     int32_t deferred;        /* 1: a level operator whose device formats are not built yet (the  *
                               * V-cycle runs a cycle-order copy): shape fields     *
                               * are valid, format fields 0 until the first compute call builds it */
+    int32_t row_seg;         /* segment length of the operator's row map: 8, 16 or 32 when its    *
+                              * formats store the rows in an order of their own (the cycle's P_0,  *
+                              * DESIGN.md 4.1; vectors, export and results are unchanged), 0: none */
 } amg_matrix_info;
 int amg_par_csr_info(amg_matrix A, amg_matrix_info* info);
 

@@ -82,6 +82,7 @@ class MatrixInfo(C.Structure):
         ("gs_split", C.c_int32),
         ("gs_chain_maxw", C.c_int32),
         ("deferred", C.c_int32),
+        ("row_seg", C.c_int32),
     ]
 
 

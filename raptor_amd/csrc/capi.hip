@@ -385,6 +385,7 @@ int amg_par_csr_info(amg_matrix A, amg_matrix_info* info) {
         info->tile_line_bytes = m.tiled && m.format != AMG_FORMAT_CSR ? 8 * m.line_w : 0;
         info->gs_split = m.gs.block > 0 && m.gs.split.on ? 1 : 0;
         info->gs_chain_maxw = info->gs_split ? m.gs.split.cmaxw[0] | m.gs.split.cmaxw[1] << 16 : 0;
+        info->row_seg = m.row_seg;
     });
 }
 
@@ -425,6 +426,7 @@ int amg_par_csr_format_digest(amg_matrix A, uint64_t* digest) {
         mix(M.vidx.p, M.vidx.n);
         mix(M.dvi.p, M.dvi.n);
         mix(M.rend.p, M.rend.n * sizeof(uint16_t));
+        if (M.row_seg > 0) mix(M.seg.p, M.seg.n * sizeof(int));  // (no map: the digest is what it was)
         *digest = h;
     });
 }

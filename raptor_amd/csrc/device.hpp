@@ -447,6 +447,19 @@ struct DevMatrix {
     // build-time only: this rank's send lists index its column level through this map (old
     // local position -> new; the cycle-order copies)
     const std::vector<int64_t>* send_map = nullptr;
+    // segment row map (DESIGN.md 4.1, P0's cycle copy): the formats hold the rows in an order
+    // of their own in which every run of row_seg stored rows is row_seg consecutive rows of the
+    // vectors (a segment); seg_rows[j] is the vector row of stored row j * row_seg.  `host`,
+    // export and every vector stay in vector order: the map is a storage detail.  Set before
+    // build (row_seg 0: none); a build that cannot use it (gather path, a long-row or empty
+    // block) clears both and stores the rows in vector order.
+    int row_seg = 0;
+    std::vector<int> seg_rows;
+    // per block: its segments' vector rows at a fixed stride of kTPB * kGatherRPB / row_seg
+    // entries (padded with the last), loaded with the block's first round
+    DevBuf<int> seg;
+    int seg_stride() const { return row_seg > 0 ? kTPB * kGatherRPB / row_seg : 0; }
+    DevBuf<int> prp;  // AMG_FORMAT_CSR of an operator with a row map: row_ptr in vector order
     DevBuf<int> pcol;
     DevBuf<double> pval;
     int plain_blocks() const { return (int)((n_rows + kTPB - 1) / kTPB); }

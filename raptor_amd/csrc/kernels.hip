@@ -601,6 +601,164 @@ __global__ __launch_bounds__(kTPB, GRPB > 1 ? 7 : 8) void csr_block_kernel(CsrAr
     block_partial<NORM>(a, bid, sq);
 }
 
+// ---- segment row map (DESIGN.md 4.1, P0's cycle copy) ----
+// The operator's rows are stored in an order of their own in which every run of S = 1 << sh
+// stored rows is S consecutive rows of y (a segment).  Block b's segments' y rows sit at
+// seg[b * stride + j], stride = kTPB * kGatherRPB / S, padded with the last: they load by block
+// id alone, with batch 1, so y's operand loads stay in the second round.
+struct RowMapArg {
+    const int* seg;
+    int sh;
+};
+
+// the y rows of a lane's block rows tid + kTPB j, and of the block's first row (lanes past the
+// block re-read it, as they re-read row r0 without a map)
+template <int RPB>
+struct RowSegs {
+    int row[RPB];
+    int first;
+};
+
+template <int RPB>
+__device__ __forceinline__ void row_segs_load(const RowMapArg& m, int bid, RowSegs<RPB>& o) {
+    const int tid = threadIdx.x;
+    const int* sg = m.seg + (size_t)bid * (size_t)((kTPB * kGatherRPB) >> m.sh);
+    const int low = tid & ((1 << m.sh) - 1);  // kTPB is a multiple of S: the same for every j
+#pragma unroll
+    for (int j = 0; j < RPB; ++j) o.row[j] = sg[(tid + kTPB * j) >> m.sh] + low;
+    o.first = sg[0];
+}
+
+// block_main's x-tile SpMV / y += Ax form (TILE, batch 1 prefetched into `pre`, no norm) with
+// the rows of y -- and the y2 / dinv operands of a restriction-style call -- taken from `ym`;
+// rend stays indexed by stored row.  The same loads, products and sums as block_main: kept
+// apart so that no instantiation of block_main changes.
+template <int MODE, bool VIB, int RPB, int LW>
+__device__ __forceinline__ void block_rowmap(const CsrArgs& a, double* stage, double* tabl, int* rends,
+                                             const CsrPre& pre, const RowSegs<RPB>& ym) {
+    constexpr int U = kCAP / kTPB;  // 8 lane slots
+    static_assert(MODE == KM_SPMV || MODE == KM_SPMV_ADD, "row map: SpMV / y += Ax only");
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid_line = pre.tid_line, tid_line2 = pre.tid_line2;
+    const v4u_t lq = pre.lq;
+    const v2u_t vq = pre.vq;
+    const int4 h0 = pre.h0, h1 = pre.h1;
+    const int r0 = h0.x, r1 = h0.y, k0 = h0.z, nnz = h0.w;
+    const int r = r0 + tid;
+    const bool own = r < r1;
+    // rows r0 + tid + kTPB j, j >= 1 (RPB > 1): ends and y operands, loaded with batch 2 (the
+    // ends are read back from LDS for the sums: the y rows take their registers)
+    double pxm[RPB];
+#pragma unroll
+    for (int j = 1; j < RPB; ++j) {
+        const int rj = r0 + tid + kTPB * j;
+        const bool in = rj < r1;
+        const int yj = in ? ym.row[j] : ym.first;
+        rends[tid + kTPB * j] = a.rend[in ? rj : r0];
+        pxm[j] = MODE == KM_SPMV_ADD ? a.y[yj] : a.y2 ? a.dinv[yj] : 0.0;
+    }
+    double v[U], tv = 0.0;
+    if (VIB) {
+        tv = a.vtab[h1.z + min(tid, h1.w - 1)];
+    } else {
+        const int plast = (nnz - 1) & ~1;
+#pragma unroll
+        for (int p = 0; p < U / 2; ++p) {
+            const v2d_t vv = __builtin_nontemporal_load((const v2d_t*)(a.val + k0 + min(2 * tid + 2 * kTPB * p, plast)));
+            v[2 * p] = vv.x;
+            v[2 * p + 1] = vv.y;
+        }
+    }
+    const int rr = own ? r : r0, yr = own ? ym.row[0] : ym.first;
+    const int e1 = a.rend[rr];
+    rends[tid] = e1;
+    double pd = 0.0, px = 0.0;
+    if (MODE == KM_SPMV_ADD) px = a.y[yr];
+    if (MODE == KM_SPMV && a.y2) pd = a.dinv[yr];  // store_y2
+    __builtin_amdgcn_sched_barrier(0);
+    double xs[U];
+    const int e = LW == 8 ? 2 * (lane & 3) : 2 * (lane & 1);
+    auto line_of_pair = [&](int j) {
+        return LW == 8 ? __shfl(tid_line, (lane >> 2) + 16 * j, 64)
+                       : __shfl(j < 2 ? tid_line : tid_line2, (lane >> 1) + 32 * (j & 1), 64);
+    };
+    if (a.wide_x) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int L = line_of_pair(j);
+            const v2d_t p2 = L < a.hl0 ? load_pair(a.x, L * LW + e, a.ncl)
+                                       : load_pair(a.xh, (L - a.hl0) * LW + e, a.nhalo);
+            xs[2 * j] = p2.x;
+            xs[2 * j + 1] = p2.y;
+        }
+    } else {  // a vector of one entry: 8-byte loads (degenerate coarse partitions)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int L = line_of_pair(j);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const double* p = L < a.hl0 ? a.x + min(L * LW + e + h, a.ncl - 1)
+                                            : a.xh + min((L - a.hl0) * LW + e + h, a.nhalo - 1);
+                xs[2 * j + h] = *p;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        *(v2d_t*)(stage + 2 * tid + 512 * j) = v2d_t{xs[2 * j], xs[2 * j + 1]};
+    if (VIB) tabl[tid] = tv;
+    __syncthreads();
+    if (VIB) {
+        const unsigned w[2] = {vq.x, vq.y};
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = tabl[(w[u >> 2] >> (8 * (u & 3))) & 0xffu];
+    }
+    double pr[U];
+    const unsigned li[U] = {lq.x & 0xffffu, lq.x >> 16, lq.y & 0xffffu, lq.y >> 16,
+                            lq.z & 0xffffu, lq.z >> 16, lq.w & 0xffffu, lq.w >> 16};
+#pragma unroll
+    for (int u = 0; u < U; ++u) pr[u] = v[u] * stage[li[u]];
+    __syncthreads();  // every lane has read the tile; reuse it for the products
+#pragma unroll
+    for (int p = 0; p < U / 2; ++p) *(v2d_t*)(stage + 2 * tid + 2 * kTPB * p) = v2d_t{pr[2 * p], pr[2 * p + 1]};
+    __syncthreads();
+#pragma unroll
+    for (int j = 1; j < RPB; ++j) {
+        const int k = tid + kTPB * j;
+        if (r0 + k < r1) {
+            const double sj = lds_row_sum(stage, rends[k - 1], rends[k], 0.0);
+            a.y[ym.row[j]] = MODE == KM_SPMV ? sj : pxm[j] + sj;
+            store_y2<MODE>(a, ym.row[j], sj, pxm[j]);
+        }
+    }
+    const int e0 = tid ? rends[tid - 1] : 0;
+    const double s = lds_row_sum(stage, e0, e1, 0.0);
+    const double out = MODE == KM_SPMV ? s : px + s;
+    if (own) {
+        a.y[yr] = out;
+        store_y2<MODE>(a, yr, out, pd);
+    }
+}
+
+// The x-tile block kernel of an operator with a segment row map.  The builder gives such an
+// operator only tile blocks (no long-row or empty block), so there is no block_long path.
+template <int MODE, bool XCD, bool VI, int GRPB, int LW>
+__global__ __launch_bounds__(kTPB, GRPB > 1 ? 7 : 8) void csr_block_rowmap_kernel(CsrArgs a, int first_block,
+                                                                                 RowMapArg m) {
+    static_assert(kCAP / kTPB == 8 && (LW == 8 || LW == 4) && kTPB == 256,
+                  "lane-major layouts assume 8 entries per lane, 4 waves");
+    __shared__ __attribute__((aligned(16))) double stage[kCAP];  // x tile, then products
+    __shared__ double tabl[VI ? 256 : 1];
+    __shared__ int rends[kTPB * GRPB];
+    const int bid = first_block + (XCD ? xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x);
+    CsrPre f;
+    csr_pre_tile<VI, LW>(a, bid, f);
+    RowSegs<GRPB> ys;
+    row_segs_load<GRPB>(m, bid, ys);
+    if (VI && f.h1.z >= 0) block_rowmap<MODE, true, GRPB, LW>(a, stage, tabl, rends, f, ys);
+    else block_rowmap<MODE, false, GRPB, LW>(a, stage, tabl, rends, f, ys);
+}
+
 // Plain CSR (AMG_FORMAT_CSR): exactly the arrays SURVEY.md 8(d) prices --
 // int32 row_ptr, int32 col, fp64 val -- and nothing else (no headers, tiles, value indexing
 // or templates).  It is the roofline leg scored on 8(d)'s algorithmic bytes, and the path for
@@ -2294,7 +2452,23 @@ void launch_tpl(hipStream_t s, int mode, bool norm, const DevMatrix& A, const do
 }
 
 template <int M, bool N, bool X, bool T, bool V>
-static void launch_block(hipStream_t s, dim3 g, const CsrArgs& a, int first_block, bool rpb4, int lw) {
+static void launch_block(hipStream_t s, dim3 g, const CsrArgs& a, int first_block, bool rpb4, int lw,
+                         const RowMapArg& rm) {
+    if (rm.seg) {  // an operator with a segment row map: the x-tile SpMV forms only
+        if constexpr (T && !N && (M == KM_SPMV || M == KM_SPMV_ADD)) {
+#define AMG_RM(G, L) hipLaunchKernelGGL((csr_block_rowmap_kernel<M, X, V, G, L>), g, dim3(kTPB), 0, s, a, first_block, rm)
+            if (lw == 4) {
+                if (rpb4) AMG_RM(kGatherRPB, 4);
+                else AMG_RM(1, 4);
+            } else {
+                if (rpb4) AMG_RM(kGatherRPB, 8);
+                else AMG_RM(1, 8);
+            }
+#undef AMG_RM
+            return;
+        }
+        throw Error(AMG_ERR_INTERNAL, "row-mapped operator: no kernel for this mode / variant");
+    }
     if constexpr (T) {
         if (lw == 4) {  // 32-byte x-tile lines
             if constexpr (!N && (M == KM_SPMV || M == KM_SPMV_ADD)) {
@@ -2336,7 +2510,13 @@ void launch_csr_stream(hipStream_t s, int mode, bool norm, const DevMatrix& A, i
     const int var = kernel_variant(A);
     if (var & KV_C16) a.col16 = A.col16.p;
     const bool rpb4 = A.gather_rpb > 1;
-#define AMG_L1(M, N, X, T, V) launch_block<M, N, X, T, V>(s, g, a, first_block, rpb4, A.line_w)
+    RowMapArg rm{nullptr, 0};
+    if (A.row_seg > 0) {
+        AMG_ASSERT(A.seg.p != nullptr);
+        rm.seg = A.seg.p;
+        while ((1 << rm.sh) < A.row_seg) ++rm.sh;
+    }
+#define AMG_L1(M, N, X, T, V) launch_block<M, N, X, T, V>(s, g, a, first_block, rpb4, A.line_w, rm)
 #define AMG_L2(M, N, V)                                               \
     do {                                                              \
         const bool xo = var & KV_XCD, tl = !(var & KV_GATHER);        \
@@ -2411,7 +2591,7 @@ void launch_csr_plain(hipStream_t s, int mode, bool norm, const DevMatrix& A, co
     const int g = A.plain_blocks();
     if (g <= 0) return;
     AMG_ASSERT(A.pcol.p != nullptr && A.pval.p != nullptr);
-    PlainArgs a{A.rp.p, A.pcol.p, A.pval.p, x, A.halo.p, (int)A.n_cols_local, (int)A.n_rows,
+    PlainArgs a{A.prp.p ? A.prp.p : A.rp.p, A.pcol.p, A.pval.p, x, A.halo.p, (int)A.n_cols_local, (int)A.n_rows,
                 b, A.dinv.p, y, omega, partial, xprev, c1};
 #define AMG_PL(M, N) hipLaunchKernelGGL((csr_plain_kernel<M, N>), dim3(g), dim3(kTPB), 0, s, a)
     switch (mode) {

@@ -138,9 +138,37 @@ struct CycleOrder {
     std::vector<char> on;                          // per level: permuted (the same on every rank)
     std::vector<std::vector<int64_t>> perm, inv;   // this rank's points: new -> old, old -> new
     std::vector<int64_t> at;                       // fine point of each point of the last level seen
+    // AMG_P0_ROWMAP = 0 / 8 / 16 / 32: segment length S of the row order P_0's cycle copy is
+    // stored in while level 0 itself stays in the hierarchy's order (0: none)
+    static constexpr int kP0Seg = 16;
+    int p0_seg = kP0Seg;
+    int64_t n0 = 0;  // level-0 local rows
+
+    // The stored row order of P_0's cycle copy: S x 8 x 8 bricks of this rank's grid in level 1's
+    // brick sequence, inside a brick z, then y, then x.  Returns the level-0 row of every run of
+    // S stored rows (a segment: S consecutive points of one grid line); empty: no map (level 1
+    // not permuted, or the x extent no multiple of S).
+    std::vector<int> p0_segments() const {
+        std::vector<int> seg;
+        const int64_t S = p0_seg, gz = std::max<int64_t>(g[2], 1);
+        if (S <= 0 || !any(1) || any(0) || g[0] % S != 0 || g[0] * g[1] * gz != n0) return seg;
+        seg.reserve((size_t)(n0 / S));
+        for (int64_t bz = 0; bz < gz; bz += kB)
+            for (int64_t by = 0; by < g[1]; by += kB)
+                for (int64_t bx = 0; bx < g[0]; bx += S)
+                    for (int64_t z = bz; z < std::min(bz + kB, gz); ++z)
+                        for (int64_t y = by; y < std::min(by + kB, g[1]); ++y)
+                            seg.push_back((int)((z * g[1] + y) * g[0] + bx));
+        return seg;
+    }
 
     void init(const DevMatrix& A, const amg_options& opt, const HostComm& comm, size_t maxl) {
         const char* e = std::getenv("AMG_CYCLE_ORDER");  // read per setup (tests compare both)
+        if (const char* r = std::getenv("AMG_P0_ROWMAP")) {
+            p0_seg = std::atoi(r);
+            AMG_CHECK(p0_seg == 0 || p0_seg == 8 || p0_seg == 16 || p0_seg == 32, "AMG_P0_ROWMAP must be 0, 8, 16 or 32");
+        }
+        n0 = A.n_rows;
         std::copy(A.grid_local, A.grid_local + 3, g);
         const bool mine = g[0] > 0 && g[1] > 0 && g[0] * g[1] * std::max<int64_t>(g[2], 1) >= A.n_rows;
         open = !(e && std::atoi(e) == 0) && opt.smoother == AMG_SMOOTH_JACOBI &&
@@ -278,9 +306,16 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
     // for a caller that asks for them: DevMatrix::defer)
     CycleOrder co;
     co.init(A, opt, comm, maxl);
-    auto copy = [this, &comm](const HostCSR& M, const std::vector<int64_t>& rows, const std::vector<int64_t>& cols) {
+    // segs (P_0 only): the operator's rows stay in the hierarchy's order for its callers, and the
+    // formats store them by CycleOrder::p0_segments (DevMatrix::row_seg)
+    auto copy = [this, &comm](const HostCSR& M, const std::vector<int64_t>& rows, const std::vector<int64_t>& cols,
+                              int seg_len = 0, std::vector<int> segs = {}) {
         std::unique_ptr<DevMatrix> d(new DevMatrix());
         d->blocks_only = true;  // row templates assume ascending offsets
+        if (!segs.empty()) {
+            d->row_seg = seg_len;
+            d->seg_rows = std::move(segs);
+        }
         // what this rank sends of its column level: positions in that level's order
         d->send_map = cols.empty() ? nullptr : &cols;
         d->build(ctx, permuted_csr(M, comm.rank, rows, cols));
@@ -342,7 +377,10 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
                 }
                 if (co.any(p) || co.any(a)) {
                     const HostCSR *Ph = &H.levels[p].P, *Rh = &H.levels[p].R;
-                    worker2->push([&, a, p, Ph] { prePc[p] = copy(*Ph, co.perm[p], co.inv[a]); });
+                    worker2->push([&, a, p, Ph] {
+                        prePc[p] = p == 0 ? copy(*Ph, co.perm[p], co.inv[a], co.p0_seg, co.p0_segments())
+                                          : copy(*Ph, co.perm[p], co.inv[a]);
+                    });
                     worker2->push([&, a, p, Rh] { preRc[p] = copy(*Rh, co.perm[a], co.inv[p]); });
                 } else {
                     worker2->push(job(preP[p], H.levels[p].P, -1));
@@ -416,7 +454,9 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
             const bool pa = l > 0 && co.any(l), pr = l + 1 < levels.size() && (co.any(l) || co.any(l + 1));
             if (pa) levels[l].Ac = preAc[l] ? std::move(preAc[l]) : copy(levels[l].A->host, co.perm[l], co.inv[l]);
             if (pr) {
-                levels[l].Pc = prePc[l] ? std::move(prePc[l]) : copy(levels[l].P->host, co.perm[l], co.inv[l + 1]);
+                levels[l].Pc = prePc[l] ? std::move(prePc[l])
+                               : l == 0 ? copy(levels[l].P->host, co.perm[l], co.inv[l + 1], co.p0_seg, co.p0_segments())
+                                        : copy(levels[l].P->host, co.perm[l], co.inv[l + 1]);
                 levels[l].Rc = preRc[l] ? std::move(preRc[l]) : copy(levels[l].R->host, co.perm[l + 1], co.inv[l]);
             }
         }
@@ -1277,7 +1317,9 @@ int32_t Solver::pcg(double* x, const double* b, int32_t max_iter, double tol, do
 }
 
 static int64_t spmv_bytes(const DevMatrix& M) {
-    return 12 * M.nnz + 4 * (M.n_rows + 1) + 8 * M.n_cols_local + 8 * M.n_rows;
+    // a segment row map is one more index stream of the operator: 4 B per segment
+    const int64_t map = M.row_seg > 0 ? 4 * (M.n_rows / M.row_seg) : 0;
+    return 12 * M.nnz + 4 * (M.n_rows + 1) + 8 * M.n_cols_local + 8 * M.n_rows + map;
 }
 
 int64_t Solver::bytes_per_cycle(size_t l) const {

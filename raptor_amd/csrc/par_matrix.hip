@@ -169,7 +169,11 @@ struct BlockBuild {
 static BlockBuild build_row_blocks(const std::vector<int>& rp, const hvec<int>& col,
                                    const std::vector<uint8_t>& cls, int64_t ncl, int64_t nhalo,
                                    const std::vector<uint8_t>* tplf = nullptr, int row_cap = kTPB,
-                                   bool line_cap = true, bool want_lcol = true, int lw = 8, int sample = 1) {
+                                   bool line_cap = true, bool want_lcol = true, int lw = 8, int sample = 1,
+                                   int unit = 1) {
+    // unit > 1 (an operator with a segment row map): blocks start and end on multiples of
+    // `unit` rows, and the caps are tested a whole segment at a time
+    AMG_ASSERT(unit >= 1 && (unit == 1 || tplf == nullptr));
     if (sample > 1) want_lcol = false;
     const int n = (int)rp.size() - 1;
     const int sh = lw == 8 ? 3 : 2, tl_cap = kCAP / lw;
@@ -206,7 +210,7 @@ static BlockBuild build_row_blocks(const std::vector<int>& rp, const hvec<int>& 
 #pragma omp parallel for reduction(max : max_row) schedule(static)
     for (int i = 0; i < n; ++i) max_row = std::max(max_row, rp[i + 1] - rp[i]);
     int hb = 10;
-    while (((size_t)1 << hb) < 2 * ((size_t)kCAP + 2 * (size_t)max_row)) ++hb;
+    while (((size_t)1 << hb) < 2 * ((size_t)kCAP + 2 * (size_t)max_row * (size_t)unit)) ++hb;
     const size_t H = (size_t)1 << hb;
 #pragma omp parallel if (nch > 1)
     {
@@ -240,7 +244,8 @@ static BlockBuild build_row_blocks(const std::vector<int>& rp, const hvec<int>& 
 #pragma omp for schedule(dynamic, 1)
         for (int ch = 0; ch < nch; ++ch) {
             if (ch % sample) continue;
-            const int ra = (int)((int64_t)n * ch / nch), rb = (int)((int64_t)n * (ch + 1) / nch);
+            const int ra = (int)((int64_t)n * ch / nch) / unit * unit;
+            const int rb = ch + 1 == nch ? n : (int)((int64_t)n * (ch + 1) / nch) / unit * unit;
             std::vector<Rec>& rc = recs[(size_t)ch];
             int r0 = ra, nl = 0;
             long long acc = 0;
@@ -264,12 +269,12 @@ static BlockBuild build_row_blocks(const std::vector<int>& rp, const hvec<int>& 
                 lines.clear();
                 next_block();
             };
-            // distinct lines of row r not yet in the open block (marker keeps them distinct
-            // per call)
+            // distinct lines of rows [r, r + unit) not yet in the open block (marker keeps them
+            // distinct per call)
             auto collect = [&](int r, int64_t marker) {
                 cand.clear();
                 cslot.clear();
-                for (int k = rp[r]; k < rp[r + 1]; ++k) {
+                for (int k = rp[r]; k < rp[std::min(r + unit, rb)]; ++k) {
                     const int64_t L = line_of(col[k]);
                     const size_t h = find(L);
                     if (!hin[h] && hrow[h] != marker) {
@@ -279,10 +284,10 @@ static BlockBuild build_row_blocks(const std::vector<int>& rp, const hvec<int>& 
                     }
                 }
             };
-            for (int r = ra; r < rb; ++r) {
-                const long long len = rp[r + 1] - rp[r];
+            for (int r = ra; r < rb; r += unit) {
+                const long long len = rp[std::min(r + unit, rb)] - rp[r];
                 collect(r, 2 * (int64_t)r);
-                if (r > r0 && (cls[r] != cls[r0] || acc + len > kCAP || r - r0 >= row_cap ||
+                if (r > r0 && (cls[r] != cls[r0] || acc + len > kCAP || r - r0 + unit > row_cap ||
                                (line_cap && nl + (int)cand.size() > tl_cap) ||
                                (tplf && (*tplf)[r] != (*tplf)[r0]))) {
                     emit(r0, r);  // closes [r0, r); a new generation
@@ -752,10 +757,10 @@ struct CutChoice {
 // each choice cut the whole operator again: 0.6 s of sa27's setup.
 static CutChoice choose_cut(const BuildKnobs& knobs, const std::vector<int>& hrp, const hvec<int>& hcol,
                             const std::vector<uint8_t>& cls, const std::vector<uint8_t>* tplf, int64_t n_cols_local,
-                            int64_t n_halo, bool square, int gather_rpb) {
+                            int64_t n_halo, bool square, int gather_rpb, int unit = 1) {
     constexpr int kSample = 8;
     const BlockBuild s8 = build_row_blocks(hrp, hcol, cls, n_cols_local, n_halo, tplf, kTPB * gather_rpb, true,
-                                           false, 8, kSample);
+                                           false, 8, kSample, unit);
     // rectangular operators take the x-tile kernel when their blocks reuse x lines: at most
     // 0.5 tile lines per nonzero.  Same-box A/B (profiles/r2y_rtile_*, r2z_rpb_*): 7-pt R0
     // 106 -> 79 us (0.23 lines / nnz), R1 66 -> 53 (0.34), P0 (4 rows per lane, 0.06)
@@ -797,7 +802,7 @@ static CutChoice choose_cut(const BuildKnobs& knobs, const std::vector<int>& hrp
             bool take = force == 4 || !square;
             if (!take) {
                 const BlockBuild s4 = build_row_blocks(hrp, hcol, cls, n_cols_local, n_halo, tplf,
-                                                       kTPB * gather_rpb, true, false, 4, kSample);
+                                                       kTPB * gather_rpb, true, false, 4, kSample, unit);
                 take = 5 * s4.blocks.size() <= 4 * s8.blocks.size();
             }
             if (take) cut.line_w = 4;
@@ -1061,6 +1066,20 @@ static std::vector<int4> block_headers(DevMatrix& M, const std::vector<int>& hrp
     return hh;
 }
 
+// Row map: block q's segments' vector rows at q * seg_stride(), padded with the last (the
+// kernel loads them by block id alone, like the tile line ids).  Built on the host for both
+// format builders: 4 bytes per segment.
+static void upload_block_segments(DevMatrix& M, const std::vector<int2>& blocks) {
+    const int S = M.row_seg, st = M.seg_stride();
+    std::vector<int> sg(std::max<size_t>(blocks.size(), 1) * st, 0);
+    for (size_t q = 0; q < blocks.size(); ++q) {
+        const int s0 = blocks[q].x / S, ns = (blocks[q].y - blocks[q].x) / S;
+        AMG_ASSERT(ns >= 1 && ns <= st && blocks[q].x % S == 0 && blocks[q].y % S == 0);
+        for (int j = 0; j < st; ++j) sg[q * st + j] = M.seg_rows[s0 + std::min(j, ns - 1)];
+    }
+    M.seg.upload(sg.data(), sg.size());
+}
+
 // Format bytes of one default-variant SpMV (the kernel reads every lane slot of the
 // fixed-stride streams, so their padding counts) into M.csr_fmt_bytes / M.spmv_fmt_bytes.
 // With templates: the skipped blocks cost nothing; template rows cost 1 byte (id); the
@@ -1086,6 +1105,7 @@ static void format_bytes(DevMatrix& M, const std::vector<int4>& hh, const std::v
         if (tiled) fb += 4 * (kCAP / line_w) + 2 * kCAP;  // tile ids, tile indices
         else if (M.col16.p) fb += 2 * (int64_t)nz + 16;   // column codes, band bases
         else fb += 4 * (int64_t)nz;                       // columns
+        if (M.row_seg > 0) fb += 4 * (int64_t)(kTPB * M.gather_rpb / M.row_seg);  // segment rows the lanes load
         if (hh[2 * q + 1].z >= 0)
             fb += (tiled ? kCAP : gather_slots(nz) * kTPB) + 8 * (int64_t)hh[2 * q + 1].w;
         else
@@ -1099,7 +1119,59 @@ static void format_bytes(DevMatrix& M, const std::vector<int4>& hh, const std::v
 // Every device format from a CSR the caller keeps (H, never the member `host`):
 // Solver::setup runs this on a worker thread while the hierarchy thread still reads the same
 // CSR, and moves it into `host` after both are done.
-void DevMatrix::build_view(Context* c, const HostCSR& H, bool replicated_view) {
+// An operator's segment row map, checked before anything is uploaded: every segment lies
+// inside the rows and every row belongs to exactly one (a bad map fails here, never in a kernel)
+static void check_row_map(const std::vector<int>& seg_rows, int S, int64_t n_rows) {
+    AMG_CHECK((S == 8 || S == 16 || S == 32) && n_rows % S == 0 && kTPB % S == 0, "row map: segment length");
+    AMG_CHECK((int64_t)seg_rows.size() * S == n_rows, "row map: segment count");
+    std::vector<char> seen((size_t)n_rows, 0);
+    for (const int base : seg_rows) {
+        AMG_CHECK(base >= 0 && (int64_t)base + S <= n_rows, "row map: segment outside the rows");
+        for (int k = 0; k < S; ++k) {
+            AMG_CHECK(!seen[(size_t)base + k], "row map: row covered twice");
+            seen[(size_t)base + k] = 1;
+        }
+    }
+}
+
+// H's rows in the stored order of a segment row map (stored row i = vector row
+// seg_rows[i / S] + i % S); columns, values and each row's entry order are H's
+static HostCSR rows_in_stored_order(const HostCSR& H, const std::vector<int>& seg_rows, int S) {
+    HostCSR B;
+    B.n_global_rows = H.n_global_rows;
+    B.n_global_cols = H.n_global_cols;
+    B.row_starts = H.row_starts;
+    B.col_starts = H.col_starts;
+    const int64_t n = H.nrows();
+    B.rp.assign((size_t)n + 1, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t o = seg_rows[i / S] + i % S;
+        B.rp[i + 1] = B.rp[i] + (H.rp[o + 1] - H.rp[o]);
+    }
+    B.col.resize((size_t)H.nnz());
+    B.val.resize((size_t)H.nnz());
+#pragma omp parallel for schedule(static)
+    for (int64_t j = 0; j < n / S; ++j) {  // a segment's rows are consecutive on both sides
+        const int64_t o = seg_rows[j], k0 = H.rp[o], k1 = H.rp[o + S];
+        std::copy(H.col.begin() + k0, H.col.begin() + k1, B.col.begin() + B.rp[j * S]);
+        std::copy(H.val.begin() + k0, H.val.begin() + k1, B.val.begin() + B.rp[j * S]);
+    }
+    return B;
+}
+
+void DevMatrix::build_view(Context* c, const HostCSR& Hv, bool replicated_view) {
+    // with a row map the formats are built from the rows in stored order; the caller's CSR
+    // (vector order) stays the host image
+    HostCSR stored;
+    if (row_seg > 0) {
+        AMG_CHECK(!replicated_view && blocks_only, "row map: a cycle copy only");
+        check_row_map(seg_rows, row_seg, Hv.nrows());
+        stored = rows_in_stored_order(Hv, seg_rows, row_seg);
+    }
+    const bool mapped = row_seg > 0;
+    const HostCSR& H = mapped ? stored : Hv;
+    seg.reset();
+    prp.reset();
     ctx = c;
     replicated = replicated_view;
     static const HostComm serial;  // rank 0 of 1: replicated matrices have no halo
@@ -1125,43 +1197,73 @@ void DevMatrix::build_view(Context* c, const HostCSR& H, bool replicated_view) {
     std::vector<int> hrp;
     hvec<int> hcol;
     std::vector<uint8_t> cls;
-    local_columns(H, plan, first_col, n_cols_local, hrp, hcol, cls);
-    rp.upload(hrp.data(), hrp.size());
     std::vector<double> di;
-    if (square) {
-        std::vector<double> d = diagonal(comm, H);
-        di.resize(n_rows);
-#pragma omp parallel for schedule(static)
-        for (int64_t i = 0; i < n_rows; ++i) di[i] = 1.0 / d[i];
-        dinv.upload(di.data(), di.size());
-    }
     TplBuild tb;
-    tpl = TplFormat{};
-    nb_skip = 0;
-    if (square && n_rows > 0 && !blocks_only) tb = select_templates(knobs, H, hrp, hcol, di, n_cols_local);
-    tm.lap("    build: local columns, dinv, templates");
-    hcol.resize(nnz + kPad, 0);  // within the capacity local_columns reserved
-
     std::vector<uint8_t> tplf;
-    if (!tb.hdr.empty()) {
-        tplf.resize(n_rows);
-        for (int64_t i = 0; i < n_rows; ++i) tplf[i] = tb.id[i] != kTplNone && cls[i] == 0;
-    }
-    const std::vector<uint8_t>* tplf_p = tplf.empty() ? nullptr : &tplf;
-    // square operators: x tiles, one row per lane; short-row rectangular ones (gather
-    // path): up to kGatherRPB rows per lane (profiles/r2n: P0 x += P e 162 -> 95 us; R
-    // with 7+ entries per row was slower that way: R0 94 -> 106 us, sa27 R0 350 -> 415)
-    gather_rpb = !square && nnz <= 4 * n_rows ? kGatherRPB : 1;
+    const std::vector<uint8_t>* tplf_p = nullptr;
     const bool dev_fmt = device_formats();
-    const CutChoice cut = choose_cut(knobs, hrp, hcol, cls, tplf_p, n_cols_local, plan.n_halo(), square, gather_rpb);
-    tiled = cut.tiled;
-    tm.lap("    build: row blocks, sampled cuts");
-    // The gather kernel reads x from global memory: its blocks need only the kCAP-entry and
-    // row caps, not the 256-line tile cap.  sa27's R1 (270 entries per row over ~200 lines
-    // each) was cut into blocks of ~1 row by that cap: one lane summing while 255 idled.
-    const bool line_cap = tiled;
-    BlockBuild bb = build_row_blocks(hrp, hcol, cls, n_cols_local, plan.n_halo(), tplf_p, kTPB * gather_rpb,
-                                     line_cap, !dev_fmt, cut.line_w);
+    CutChoice cut;
+    BlockBuild bb;
+    // the cut runs once; a second time, on the rows in vector order, only when it refuses a row map
+    for (;;) {
+        local_columns(H, plan, first_col, n_cols_local, hrp, hcol, cls);
+        if (row_seg > 0) {  // a segment is cut as one: boundary class when any of its rows is
+            for (int64_t j = 0; j < n_rows / row_seg; ++j) {
+                uint8_t b = 0;
+                for (int k = 0; k < row_seg; ++k) b |= cls[j * row_seg + k];
+                for (int k = 0; k < row_seg; ++k) cls[j * row_seg + k] = b;
+            }
+        }
+        rp.upload(hrp.data(), hrp.size());
+        if (square) {
+            std::vector<double> d = diagonal(comm, H);
+            di.resize(n_rows);
+#pragma omp parallel for schedule(static)
+            for (int64_t i = 0; i < n_rows; ++i) di[i] = 1.0 / d[i];
+            dinv.upload(di.data(), di.size());
+        }
+        tpl = TplFormat{};
+        nb_skip = 0;
+        if (square && n_rows > 0 && !blocks_only) tb = select_templates(knobs, H, hrp, hcol, di, n_cols_local);
+        tm.lap("    build: local columns, dinv, templates");
+        hcol.resize(nnz + kPad, 0);  // within the capacity local_columns reserved
+
+        if (!tb.hdr.empty()) {
+            tplf.resize(n_rows);
+            for (int64_t i = 0; i < n_rows; ++i) tplf[i] = tb.id[i] != kTplNone && cls[i] == 0;
+        }
+        tplf_p = tplf.empty() ? nullptr : &tplf;
+        // square operators: x tiles, one row per lane; short-row rectangular ones (gather
+        // path): up to kGatherRPB rows per lane (profiles/r2n: P0 x += P e 162 -> 95 us; R
+        // with 7+ entries per row was slower that way: R0 94 -> 106 us, sa27 R0 350 -> 415)
+        gather_rpb = !square && nnz <= 4 * n_rows ? kGatherRPB : 1;
+        const int unit = row_seg > 0 ? row_seg : 1;
+        cut = choose_cut(knobs, hrp, hcol, cls, tplf_p, n_cols_local, plan.n_halo(), square, gather_rpb, unit);
+        tiled = cut.tiled;
+        tm.lap("    build: row blocks, sampled cuts");
+        // The gather kernel reads x from global memory: its blocks need only the kCAP-entry and
+        // row caps, not the 256-line tile cap.  sa27's R1 (270 entries per row over ~200 lines
+        // each) was cut into blocks of ~1 row by that cap: one lane summing while 255 idled.
+        const bool line_cap = tiled;
+        bool map_ok = row_seg == 0 || (tiled && !square);
+        if (map_ok) {
+            bb = build_row_blocks(hrp, hcol, cls, n_cols_local, plan.n_halo(), tplf_p, kTPB * gather_rpb, line_cap,
+                                  !dev_fmt, cut.line_w, 1, unit);
+            // csr_block_rowmap_kernel has no long-row / empty-block path: every block must be a
+            // tile block of whole segments
+            for (size_t q = 0; map_ok && row_seg > 0 && q < bb.blocks.size(); ++q) {
+                const int2 b = bb.blocks[q];
+                const int nz = hrp[b.y] - hrp[b.x], nt = bb.tile_ptr[q + 1] - bb.tile_ptr[q];
+                map_ok = nz > 0 && nz <= kCAP && nt > 0 && nt <= kCAP / cut.line_w && b.x % row_seg == 0 &&
+                         b.y % row_seg == 0 && b.y - b.x <= kTPB * gather_rpb;
+            }
+        }
+        if (map_ok) break;
+        // refused: the operator is built as without a map, rows in vector order
+        row_seg = 0;
+        seg_rows.clear();
+        stored = Hv;
+    }
     line_w = cut.line_w;
     nb_int = bb.nb_int;
     nb_bnd = bb.nb_bnd;
@@ -1202,6 +1304,7 @@ void DevMatrix::build_view(Context* c, const HostCSR& H, bool replicated_view) {
     if (!tiled && nbk > 0) gather_codes(hrp, hcol, bb.blocks, koff, col16, gband);
     const std::vector<int4> hh = block_headers(*this, hrp, bb, koff, fi);
     hdr.upload(hh.data(), hh.size());
+    if (row_seg > 0) upload_block_segments(*this, bb.blocks);
     // measured (profiles/r1m_variants.txt): x tiles in XCD order on square operators (A0
     // -6..8%, A1 -6..8%, A2 +1% vs plain order; gathers are 1.3-1.9x slower); gathers in
     // XCD order on the rectangular P / R (R0 -10% vs plain order)
@@ -1674,12 +1777,17 @@ void DevMatrix::set_format(int f) {
         }
         pcol.upload(pc.data(), pc.size());
         pval.upload(pv.data(), pv.size());
+        if (row_seg > 0) {  // `rp` follows the stored rows; the plain kernel walks the vector's
+            std::vector<int> pr(host.rp.begin(), host.rp.end());
+            prp.upload(pr.data(), pr.size());
+        }
     }
     if (f != AMG_FORMAT_CSR) {
         // the plain arrays (12 B per nonzero) are rebuilt when CSR is selected again; hipFree
         // waits for the kernels that may still read them
         pcol.reset();
         pval.reset();
+        prp.reset();
     }
     if (format != f) ++format_generation;
     format = f;
