@@ -23,15 +23,21 @@
 namespace amg {
 
 // Phase trace of the x-tile block kernel (diagnostic build only: make EXTRA=-DAMG_CSR_PHASES=1;
-// scripts/csr_phase_trace.py).  Thread 0 of each block waits for its own outstanding loads at
-// fixed points and stamps s_memtime there: [0] entry, [1] batch 1 in (header, line ids, tile /
-// VI indices), [2] batch 2 in (x tile, value table, row operands), [3] x tile in LDS (first
-// barrier passed), [4] products in LDS (second barrier), [5] row sums stored; [6] / [7]
-// s_memrealtime (100 MHz) at entry and exit.  The waits serialise thread 0's loads a little.
+// scripts/csr_phase_trace.py).  Thread 0 of each block stamps s_memtime at fixed points: [0]
+// entry, [1] batch 1 in (header, line ids, tile / VI indices), [2] x tile and value table on
+// their way to LDS, [9] thread 0's row ends and epilogue operands in as well (ahead of the
+// first barrier), [3] first barrier passed, [8] the row ends' store beside the products, [4]
+// products in LDS (third barrier), [5] row sums stored; [6] / [7] s_memrealtime (100 MHz) at
+// entry and exit.  [2] and [8] are taken where the kernel stands, behind the waits its own code
+// needed there: [8] cannot come before the products, whenever the operands arrived.  The
+// others wait for all of thread 0's outstanding loads first, which serialises them a little:
+// [9] holds thread 0's wave at the first barrier until its operands are in (the product build
+// waits for them only at [8]); [3] waited for them right behind the barrier before [9] existed.
 #ifndef AMG_CSR_PHASES
 #define AMG_CSR_PHASES 0
 #endif
 #if AMG_CSR_PHASES
+constexpr int kPhaseSlots = 10;  // stamps per block
 __device__ unsigned long long* g_csr_phase;
 #define AMG_PHASE(k)                                                   \
     do {                                                               \
@@ -40,9 +46,20 @@ __device__ unsigned long long* g_csr_phase;
             csr_ph[k] = __builtin_amdgcn_s_memtime();                  \
         }                                                              \
     } while (0)
+// stamp k where the kernel stands, behind the waits its own code needed there
+#define AMG_PHASE_HERE(k)                                        \
+    do {                                                         \
+        if (threadIdx.x == 0) {                                  \
+            asm volatile("" ::: "memory");                       \
+            csr_ph[k] = __builtin_amdgcn_s_memtime();            \
+        }                                                        \
+    } while (0)
 #else
 #define AMG_PHASE(k) \
     do {             \
+    } while (0)
+#define AMG_PHASE_HERE(k) \
+    do {                  \
     } while (0)
 #endif
 
@@ -195,15 +212,6 @@ typedef unsigned int v4u_t __attribute__((ext_vector_type(4)));
 typedef double v2d_t __attribute__((ext_vector_type(2)));
 typedef int v2i_t __attribute__((ext_vector_type(2)));
 
-
-// Entries [q, q+1] of a vector of n >= 2 doubles: a 16-byte load at min(q, n - 2); when q is
-// the last entry its value is the second half.  Entries past n are garbage (never used).
-__device__ __forceinline__ v2d_t load_pair(const double* base, int q, int n) {
-    const int st = min(q, n - 2);
-    const v2d_t v = *(const v2d_t*)(base + st);
-    return v2d_t{q == st ? v.x : v.y, v.y};
-}
-
 // One workgroup per row block (<= kCAP nonzeros, <= kTPB rows).  Bit-identical to the oracle:
 // products a_ij * x_j are formed in registers, staged in LDS, and lane r sums its row's
 // products in CSR order before the fused epilogue.
@@ -216,8 +224,10 @@ __device__ __forceinline__ v2d_t load_pair(const double* base, int q, int n) {
 // latency-bound (profiles/r1h_variants.txt: 278 -> 184 us on the 256^3 level-0 SpMV).
 //   batch 1 (block id only): header (scalar), one x-tile line id per lane (fixed stride),
 //            16-bit tile indices, VI indices
-//   batch 2: x tile (16-byte loads, 4 per lane; line ids via ds_bpermute), values or VI
-//            table, row bounds and epilogue operands  [gather: columns, then x]
+//   batch 2: x tile (16-byte loads, 4 per lane; line ids via ds_bpermute), then values or VI
+//            table, then row bounds and epilogue operands (vector loads return in order and
+//            only the tile and the table stand before the first barrier; block_main)
+//            [gather: row bounds and operands, columns and values, then x]
 // PMC (SQ_WAIT_INST_ANY ~42% of wave cycles) showed the VMEM issue queue, not HBM, as the
 // limit, so the per-wave vector-memory instruction count is kept low (10 for SpMV).
 //
@@ -257,6 +267,59 @@ __device__ __forceinline__ void csr_pre_tile(const CsrArgs& a, int bid, CsrPre& 
     p.vq = v2u_t{0u, 0u};
     // square operators with value-indexed blocks hold kCAP index bytes for every block
     if (VI) p.vq = __builtin_nontemporal_load((const v2u_t*)(a.vidx + (size_t)bid * kCAP + (size_t)tid * (kCAP / kTPB)));
+}
+
+// Issues a lane's x-tile loads: slot pair j of lane l is elements e, e + 1 of its line
+// (tile_id_index), e = 2 (l & 3) (64-byte lines) or 2 (l & 1) (32-byte lines); element e of line
+// L is column LW L + e (local) or halo entry LW (L - hl0) + e.  Entries [q, q + 1] of a vector of
+// n >= 2 doubles are a 16-byte load at min(q, n - 2): when q is the last entry its value is the
+// second half (what lies past n is garbage, never used).  xs[2 j], xs[2 j + 1] receive the
+// loaded pair; the slot pair is {xlo[j] ? xs[2 j] : xs[2 j + 1], xs[2 j + 1]}, selected by the
+// caller once the loads are in, so that the four loads go out back to back.
+template <int LW>
+__device__ __forceinline__ void x_tile_loads(const CsrArgs& a, int tid_line, int tid_line2, double (&xs)[kCAP / kTPB],
+                                             bool (&xlo)[4]) {
+    const int lane = threadIdx.x & 63;
+    const int e = LW == 8 ? 2 * (lane & 3) : 2 * (lane & 1);
+    auto line_of_pair = [&](int j) {
+        return LW == 8 ? __shfl(tid_line, (lane >> 2) + 16 * j, 64)
+                       : __shfl(j < 2 ? tid_line : tid_line2, (lane >> 1) + 32 * (j & 1), 64);
+    };
+    if (a.wide_x) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int L = line_of_pair(j);
+            const bool loc = L < a.hl0;
+            const int q = (loc ? L : L - a.hl0) * LW + e, st = min(q, (loc ? a.ncl : a.nhalo) - 2);
+            const v2d_t p2 = *(const v2d_t*)((loc ? a.x : a.xh) + st);
+            xs[2 * j] = p2.x;
+            xs[2 * j + 1] = p2.y;
+            xlo[j] = q == st;
+        }
+    } else {  // a vector of one entry: 8-byte loads (degenerate coarse partitions)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int L = line_of_pair(j);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const double* p = L < a.hl0 ? a.x + min(L * LW + e + h, a.ncl - 1)
+                                            : a.xh + min((L - a.hl0) * LW + e + h, a.nhalo - 1);
+                xs[2 * j + h] = *p;
+            }
+            xlo[j] = true;
+        }
+    }
+}
+
+// The tile's slot pairs for LDS.  The empty asm holds the selects here, behind the loads the
+// caller issued after the tile's: the optimiser otherwise folds them into x_tile_loads' 16-byte
+// branch, where they wait for the tile before anything else is issued.
+__device__ __forceinline__ void x_tile_to_lds(double* stage, double (&xs)[kCAP / kTPB], const bool (&xlo)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        asm volatile("" : "+v"(xs[2 * j]));
+        *(v2d_t*)(stage + 2 * threadIdx.x + 512 * j) = v2d_t{xlo[j] ? xs[2 * j] : xs[2 * j + 1], xs[2 * j + 1]};
+    }
 }
 
 // PRE: 0 = load batch 1 here; 1 / 2 = batch 1 was issued with the header into *pre (2: with
@@ -310,18 +373,32 @@ __device__ __forceinline__ double block_main(const CsrArgs& a, int bid, double* 
     const int r0 = h0.x, r1 = h0.y, k0 = h0.z, nnz = h0.w;
     const int r = r0 + tid;
     const bool own = r < r1;
+    // The x tile's loads need the line ids alone, so the x-tile path issues them first.  Vector
+    // loads return in order: whatever is issued ahead of the tile stands between it and the
+    // first barrier.  The loads whose addresses come from the header follow the tile: the value
+    // table or the values, which the products need, then the row ends and epilogue operands,
+    // which only the row sums need -- those are published with the products.
+    double xs[U];
+    bool xlo[4];  // x_tile_loads
+    if constexpr (TILE) {
+        x_tile_loads<LW>(a, tid_line, tid_line2, xs, xlo);
+        __builtin_amdgcn_sched_barrier(0);  // the tile's loads stay ahead of the header's
+    }
     // rows r0 + tid + kTPB j, j >= 1 (RPB > 1): ends and y operands, loaded with batch 2
     int e1m[RPB > 1 ? RPB : 1];
     double pxm[RPB > 1 ? RPB : 1];
-    if constexpr (RPB > 1) {
+    auto more_rows = [&]() {
+        if constexpr (RPB > 1) {
 #pragma unroll
-        for (int j = 1; j < RPB; ++j) {
-            const int rj = r0 + tid + kTPB * j, rjj = rj < r1 ? rj : r0;
-            e1m[j] = a.rend[rjj];
-            rends[tid + kTPB * j] = e1m[j];
-            pxm[j] = MODE == KM_SPMV_ADD ? a.y[rjj] : MODE == KM_SPMV && a.y2 ? a.dinv[rjj] : 0.0;
+            for (int j = 1; j < RPB; ++j) {
+                const int rj = r0 + tid + kTPB * j, rjj = rj < r1 ? rj : r0;
+                e1m[j] = a.rend[rjj];
+                if (!TILE) rends[tid + kTPB * j] = e1m[j];
+                pxm[j] = MODE == KM_SPMV_ADD ? a.y[rjj] : MODE == KM_SPMV && a.y2 ? a.dinv[rjj] : 0.0;
+            }
         }
-    }
+    };
+    if constexpr (!TILE) more_rows();
     // Entry-to-lane map.  TILE: lane t holds entries 512 p + 2 t + {0, 1} (p < 4) of the
     // block-aligned val stream (k0 even): 16-byte value loads (profiles/r1o_libab.txt: A2
     // SpMV / Jacobi -8% / -9%).  Gather: lane t holds entries t + 256 u, so one wave-
@@ -359,9 +436,13 @@ __device__ __forceinline__ double block_main(const CsrArgs& a, int bid, double* 
     }
     // row operands (lanes past the block re-read row r0); row start = previous lane's end,
     // exchanged through LDS behind the first barrier
+    if constexpr (TILE) {
+        __builtin_amdgcn_sched_barrier(0);  // the table / values stay ahead of the row operands
+        more_rows();
+    }
     const int rr = own ? r : r0;
     const int e1 = a.rend[rr];
-    rends[tid] = e1;
+    if (!TILE) rends[tid] = e1;
     const bool px_tile = TILE && kJacobiOperands<MODE> && h1.x >= 0;       // block-uniform
     const bool pd_tab = VIB && kJacobiOperands<MODE> && (h1.y & kHdrDvi) != 0;  // block-uniform
     double pb = 0.0, pd = 0.0, px = 0.0, pp = 0.0;
@@ -377,55 +458,24 @@ __device__ __forceinline__ double block_main(const CsrArgs& a, int bid, double* 
     // Chebyshev: the row's own entry of the iterate before x (kernel-uniform null test); y may
     // alias it, so a lane without a row discards what it re-read of row r0
     if (MODE == KM_CHEBY && a.xprev) pp = a.xprev[rr];
-    // the scheduling barrier keeps every earlier load issued before the first x load waits
-    // for its line / column id
+    // the scheduling barrier keeps every earlier load issued before the tile's first LDS store
+    // waits for it (gather path: before the first x load waits for its column id)
     __builtin_amdgcn_sched_barrier(0);
-    double xs[U];
     if (TILE) {
-        // slot pair j of lane l: elements e, e + 1 of its line (tile_id_index), e = 2 (l & 3)
-        // (64-byte lines) or 2 (l & 1) (32-byte lines); element e of line L is column
-        // LW L + e (local) or halo entry LW (L - hl0) + e
-        const int e = LW == 8 ? 2 * (lane & 3) : 2 * (lane & 1);
-        auto line_of_pair = [&](int j) {
-            return LW == 8 ? __shfl(tid_line, (lane >> 2) + 16 * j, 64)
-                           : __shfl(j < 2 ? tid_line : tid_line2, (lane >> 1) + 32 * (j & 1), 64);
-        };
-        if (a.wide_x) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int L = line_of_pair(j);
-                const v2d_t p2 = L < a.hl0 ? load_pair(a.x, L * LW + e, a.ncl)
-                                           : load_pair(a.xh, (L - a.hl0) * LW + e, a.nhalo);
-                xs[2 * j] = p2.x;
-                xs[2 * j + 1] = p2.y;
-            }
-        } else {  // a vector of one entry: 8-byte loads (degenerate coarse partitions)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int L = line_of_pair(j);
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const double* p = L < a.hl0 ? a.x + min(L * LW + e + h, a.ncl - 1)
-                                                : a.xh + min((L - a.hl0) * LW + e + h, a.nhalo - 1);
-                    xs[2 * j + h] = *p;
-                }
-            }
-        }
-        if constexpr (PRE > 0) AMG_PHASE(2);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            *(v2d_t*)(stage + 2 * tid + 512 * j) = v2d_t{xs[2 * j], xs[2 * j + 1]};
+        x_tile_to_lds(stage, xs, xlo);
     } else {
 #pragma unroll
         for (int u = 0; u < NU; ++u) xs[u] = xload(a, c[u]);
     }
     if (VIB) tabl[tid] = tv;
+    if constexpr (PRE > 0) AMG_PHASE_HERE(2);
+    if constexpr (PRE > 0) AMG_PHASE(9);
     if (TILE || VIB) __syncthreads();
     if constexpr (PRE > 0) AMG_PHASE(3);
     constexpr int LS = LW == 8 ? 3 : 2;
     if (px_tile) px = stage[(h1.x + (rr >> LS) - (r0 >> LS)) * LW + (rr & (LW - 1))];
     // 1 / a_ii from the table: the same correctly rounded division the host does for dinv
-    if (pd_tab) pd = 1.0 / tabl[dv];
+    if (!TILE && pd_tab) pd = 1.0 / tabl[dv];
     if (VIB) {
         const unsigned w[2] = {vq.x, vq.y};
 #pragma unroll
@@ -452,6 +502,15 @@ __device__ __forceinline__ double block_main(const CsrArgs& a, int bid, double* 
     } else {
 #pragma unroll
         for (int u = 0; u < NU; ++u) stage[tid + u * kTPB] = pr[u];
+    }
+    if constexpr (TILE) {  // the first use of a load that followed the tile
+        rends[tid] = e1;
+        if constexpr (RPB > 1) {
+#pragma unroll
+            for (int j = 1; j < RPB; ++j) rends[tid + kTPB * j] = e1m[j];
+        }
+        if (pd_tab) pd = 1.0 / tabl[dv];
+        if constexpr (PRE > 0) AMG_PHASE_HERE(8);
     }
     __syncthreads();
     if constexpr (PRE > 0) AMG_PHASE(4);
@@ -561,8 +620,10 @@ __global__ __launch_bounds__(kTPB, GRPB > 1 ? 7 : 8) void csr_block_kernel(CsrAr
         constexpr int PV = VI ? 2 : 1;
         unsigned long long* csr_ph = nullptr;
 #if AMG_CSR_PHASES
-        __shared__ unsigned long long ph_lds[8];
+        __shared__ unsigned long long ph_lds[kPhaseSlots];
         csr_ph = ph_lds;
+        if (threadIdx.x == 0)  // a block_long block leaves its phase stamps at zero
+            for (int k = 0; k < kPhaseSlots; ++k) csr_ph[k] = 0;
         if (threadIdx.x == 0) csr_ph[6] = __builtin_amdgcn_s_memrealtime();
         AMG_PHASE(0);
 #endif
@@ -584,7 +645,7 @@ __global__ __launch_bounds__(kTPB, GRPB > 1 ? 7 : 8) void csr_block_kernel(CsrAr
 #if AMG_CSR_PHASES
         if (threadIdx.x == 0 && g_csr_phase) {
             csr_ph[7] = __builtin_amdgcn_s_memrealtime();
-            for (int k = 0; k < 8; ++k) g_csr_phase[(size_t)(bid - first_block) * 8 + k] = csr_ph[k];
+            for (int k = 0; k < kPhaseSlots; ++k) g_csr_phase[(size_t)(bid - first_block) * kPhaseSlots + k] = csr_ph[k];
         }
 #endif
         return;
@@ -638,7 +699,7 @@ __device__ __forceinline__ void block_rowmap(const CsrArgs& a, double* stage, do
                                              const CsrPre& pre, const RowSegs<RPB>& ym) {
     constexpr int U = kCAP / kTPB;  // 8 lane slots
     static_assert(MODE == KM_SPMV || MODE == KM_SPMV_ADD, "row map: SpMV / y += Ax only");
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int tid_line = pre.tid_line, tid_line2 = pre.tid_line2;
     const v4u_t lq = pre.lq;
     const v2u_t vq = pre.vq;
@@ -646,17 +707,11 @@ __device__ __forceinline__ void block_rowmap(const CsrArgs& a, double* stage, do
     const int r0 = h0.x, r1 = h0.y, k0 = h0.z, nnz = h0.w;
     const int r = r0 + tid;
     const bool own = r < r1;
-    // rows r0 + tid + kTPB j, j >= 1 (RPB > 1): ends and y operands, loaded with batch 2 (the
-    // ends are read back from LDS for the sums: the y rows take their registers)
-    double pxm[RPB];
-#pragma unroll
-    for (int j = 1; j < RPB; ++j) {
-        const int rj = r0 + tid + kTPB * j;
-        const bool in = rj < r1;
-        const int yj = in ? ym.row[j] : ym.first;
-        rends[tid + kTPB * j] = a.rend[in ? rj : r0];
-        pxm[j] = MODE == KM_SPMV_ADD ? a.y[yj] : a.y2 ? a.dinv[yj] : 0.0;
-    }
+    // the x tile first, then the table / values, then the row ends and y operands (block_main)
+    double xs[U];
+    bool xlo[4];
+    x_tile_loads<LW>(a, tid_line, tid_line2, xs, xlo);
+    __builtin_amdgcn_sched_barrier(0);
     double v[U], tv = 0.0;
     if (VIB) {
         tv = a.vtab[h1.z + min(tid, h1.w - 1)];
@@ -669,43 +724,30 @@ __device__ __forceinline__ void block_rowmap(const CsrArgs& a, double* stage, do
             v[2 * p + 1] = vv.y;
         }
     }
+    __builtin_amdgcn_sched_barrier(0);
+    // rows r0 + tid + kTPB j, j >= 1 (RPB > 1): ends and y operands.  These ends go to LDS
+    // ahead of the first barrier, which they reach with the table or the values, and are read
+    // back for the sums: the y rows take their registers (ends held up to the products spill
+    // in the four-row forms)
+    int em[RPB];
+    double pxm[RPB];
+#pragma unroll
+    for (int j = 1; j < RPB; ++j) {
+        const int rj = r0 + tid + kTPB * j;
+        const bool in = rj < r1;
+        const int yj = in ? ym.row[j] : ym.first;
+        em[j] = a.rend[in ? rj : r0];
+        pxm[j] = MODE == KM_SPMV_ADD ? a.y[yj] : a.y2 ? a.dinv[yj] : 0.0;
+    }
     const int rr = own ? r : r0, yr = own ? ym.row[0] : ym.first;
     const int e1 = a.rend[rr];
-    rends[tid] = e1;
     double pd = 0.0, px = 0.0;
     if (MODE == KM_SPMV_ADD) px = a.y[yr];
     if (MODE == KM_SPMV && a.y2) pd = a.dinv[yr];  // store_y2
     __builtin_amdgcn_sched_barrier(0);
-    double xs[U];
-    const int e = LW == 8 ? 2 * (lane & 3) : 2 * (lane & 1);
-    auto line_of_pair = [&](int j) {
-        return LW == 8 ? __shfl(tid_line, (lane >> 2) + 16 * j, 64)
-                       : __shfl(j < 2 ? tid_line : tid_line2, (lane >> 1) + 32 * (j & 1), 64);
-    };
-    if (a.wide_x) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int L = line_of_pair(j);
-            const v2d_t p2 = L < a.hl0 ? load_pair(a.x, L * LW + e, a.ncl)
-                                       : load_pair(a.xh, (L - a.hl0) * LW + e, a.nhalo);
-            xs[2 * j] = p2.x;
-            xs[2 * j + 1] = p2.y;
-        }
-    } else {  // a vector of one entry: 8-byte loads (degenerate coarse partitions)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int L = line_of_pair(j);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const double* p = L < a.hl0 ? a.x + min(L * LW + e + h, a.ncl - 1)
-                                            : a.xh + min((L - a.hl0) * LW + e + h, a.nhalo - 1);
-                xs[2 * j + h] = *p;
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        *(v2d_t*)(stage + 2 * tid + 512 * j) = v2d_t{xs[2 * j], xs[2 * j + 1]};
+    for (int j = 1; j < RPB; ++j) rends[tid + kTPB * j] = em[j];
+    x_tile_to_lds(stage, xs, xlo);
     if (VIB) tabl[tid] = tv;
     __syncthreads();
     if (VIB) {
@@ -721,6 +763,7 @@ __device__ __forceinline__ void block_rowmap(const CsrArgs& a, double* stage, do
     __syncthreads();  // every lane has read the tile; reuse it for the products
 #pragma unroll
     for (int p = 0; p < U / 2; ++p) *(v2d_t*)(stage + 2 * tid + 2 * kTPB * p) = v2d_t{pr[2 * p], pr[2 * p + 1]};
+    rends[tid] = e1;
     __syncthreads();
 #pragma unroll
     for (int j = 1; j < RPB; ++j) {
@@ -2536,8 +2579,8 @@ void launch_csr_stream(hipStream_t s, int mode, bool norm, const DevMatrix& A, i
     // never freed: a static's hipFree at exit would run after the runtime's teardown
     static DevBuf<unsigned long long>& phase_buf = *new DevBuf<unsigned long long>();
     if (phase_file) {
-        if (phase_buf.n < (size_t)n_blocks * 8) phase_buf.alloc((size_t)n_blocks * 8);
-        HIP_CHECK(hipMemsetAsync(phase_buf.p, 0, sizeof(unsigned long long) * n_blocks * 8, s));
+        if (phase_buf.n < (size_t)n_blocks * kPhaseSlots) phase_buf.alloc((size_t)n_blocks * kPhaseSlots);
+        HIP_CHECK(hipMemsetAsync(phase_buf.p, 0, sizeof(unsigned long long) * n_blocks * kPhaseSlots, s));
         unsigned long long* p = phase_buf.p;
         HIP_CHECK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_csr_phase), &p, sizeof(p), 0, hipMemcpyHostToDevice, s));
         HIP_CHECK(hipStreamSynchronize(s));
@@ -2567,7 +2610,7 @@ void launch_csr_stream(hipStream_t s, int mode, bool norm, const DevMatrix& A, i
 #if AMG_CSR_PHASES
     if (phase_file) {
         HIP_CHECK(hipStreamSynchronize(s));
-        std::vector<unsigned long long> h((size_t)n_blocks * 8);
+        std::vector<unsigned long long> h((size_t)n_blocks * kPhaseSlots);
         HIP_CHECK(hipMemcpy(h.data(), phase_buf.p, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost));
         unsigned long long* z = nullptr;
         HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_csr_phase), &z, sizeof(z)));

@@ -3,11 +3,12 @@
     RAPTOR_AMD_LIB=raptor_amd/libraptor_amd_phase.so python scripts/csr_phase_trace.py [N]
 
 Needs the phase-trace build (make -C raptor_amd/csrc EXTRA=-DAMG_CSR_PHASES=1
-BUILD=build_phase OUT=../libraptor_amd_phase.so): thread 0 of every block stamps s_memtime when
-its own loads of each phase have landed (kernels.hip, AMG_PHASE) and s_memrealtime (100 MHz) at
+BUILD=build_phase OUT=../libraptor_amd_phase.so): thread 0 of every block stamps s_memtime at
+the end of each phase (kernels.hip, AMG_PHASE / AMG_PHASE_HERE) and s_memrealtime (100 MHz) at
 entry and exit.  Runs the 7-pt N^3 PMIS hierarchy's level-1 and level-2 residual and Jacobi
 (the cycle's dominant launches) three times each and prints, per operation: the median /
-mean of each phase in ns, the block lifetime, the kernel span, the mean number of live blocks
+mean of each phase in ns, when the row operands were in (from batch 1's arrival), the block
+lifetime, the kernel span, the mean number of live blocks
 (sum of lifetimes / span) and the spread of block start times.  Output: one JSON line."""
 import json
 import os
@@ -19,7 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import raptor_amd as ra  # noqa: E402
 
-PHASES = ["batch1", "batch2", "tile_to_lds", "products", "row_sums"]
+PHASES = ["batch1", "batch2", "tile_to_lds", "products", "row_sums"]  # stamps 0..5
+SLOTS = 10  # stamps per block (kernels.hip, kPhaseSlots)
 
 
 def read_launches(path):
@@ -28,14 +30,14 @@ def read_launches(path):
     while o < len(raw):
         mode, nb, n, nnz = np.frombuffer(raw, np.int64, 4, o)
         o += 32
-        st = np.frombuffer(raw, np.uint64, int(nb) * 8, o).reshape(int(nb), 8).astype(np.float64)
-        o += int(nb) * 8 * 8
+        st = np.frombuffer(raw, np.uint64, int(nb) * SLOTS, o).reshape(int(nb), SLOTS).astype(np.float64)
+        o += int(nb) * SLOTS * 8
         out.append((int(mode), int(nb), int(n), int(nnz), st))
     return out
 
 
 def summarize(st):
-    ok = st[:, 7] > 0
+    ok = (st[:, 7] > 0) & (st[:, 5] > 0)  # long-row / empty blocks leave the phase stamps at zero
     st = st[ok]
     rt0, rt1 = st[:, 6], st[:, 7]
     life_ns = (rt1 - rt0) * 10.0
@@ -46,6 +48,13 @@ def summarize(st):
         d = (st[:, k + 1] - st[:, k]) / ghz
         res[name + "_ns"] = {"median": round(float(np.median(d)), 1), "mean": round(float(d.mean()), 1),
                              "p90": round(float(np.percentile(d, 90)), 1)}
+    # from batch 1's arrival: stamp 9, thread 0's row ends and epilogue operands in (a wait of
+    # the trace build's, ahead of the first barrier), and stamp 8, the row ends' store beside
+    # the products (never before the products are done, whenever the operands arrived)
+    for name, k in (("row_operands_in_ns", 9), ("row_ends_stored_ns", 8)):
+        d = (st[:, k] - st[:, 1]) / ghz
+        res[name] = {"median": round(float(np.median(d)), 1), "mean": round(float(d.mean()), 1),
+                     "p90": round(float(np.percentile(d, 90)), 1)}
     span_ns = (rt1.max() - rt0.min()) * 10.0
     res["life_ns"] = {"median": round(float(np.median(life_ns)), 1), "mean": round(float(life_ns.mean()), 1)}
     res["span_us"] = round(span_ns / 1e3, 2)
