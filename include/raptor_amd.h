@@ -315,9 +315,39 @@ int amg_solver_cycle(amg_solver S, double* x, const double* b);
 int amg_solver_solve(amg_solver S, double* x, const double* b, int32_t max_iter, double tol,
                      double* hist, int32_t* iters);
 /* Conjugate gradients preconditioned by one V-cycle per iteration (row f3: the natural
- * caller of the cycle).  Same contract as amg_solver_solve; hist receives ||r_k||. */
+ * caller of the cycle).  Same contract as amg_solver_solve; hist receives ||r_k||.
+ * Requires a symmetric operator (and a symmetric cycle): on a nonsymmetric one it reports no
+ * error and does not converge -- on 7-point diffusion + first-order upwind convection (cell
+ * Peclet number 0.5 / 2 / 8) it stood at 3e-2 .. 4e-5 / 2e+0 .. 3e-4 / 6e+0 .. 1e-1 of the
+ * initial residual after 40 iterations, where amg_solver_bicgstab reached 1e-8 in 6 - 10
+ * (DESIGN.md 6).  Use amg_solver_bicgstab there. */
 int amg_solver_pcg(amg_solver S, double* x, const double* b, int32_t max_iter, double tol,
                    double* hist, int32_t* iters);
+/* BiCGStab for nonsymmetric operators, right-preconditioned by one V-cycle per application
+ * (M(v): one cycle on A z = v from z = 0; two applications and two products with A per
+ * iteration).  With dot the rank-ordered dot product of amg_solver_pcg:
+ *   r = b - A x; rhat = r; p = r; rr = dot(r, r); rho = rr; hist[0] = sqrt(rr)
+ *   for k = 1 .. max_iter:
+ *     phat = M(p); v = A phat; rv = dot(rhat, v)
+ *     rv == 0 or rho / rv not finite: BREAKDOWN, stop (nothing written, k not counted)
+ *     alpha = rho / rv; s = r - alpha v
+ *     shat = M(s); t = A shat; omega = dot(t, s) / dot(t, t)   (0 if dot(t, t) == 0 or not finite)
+ *     x = (x + alpha phat) + omega shat; r = s - omega t
+ *     rr = dot(r, r); rho' = dot(rhat, r); hist[k] = sqrt(rr)   (iteration k is counted)
+ *     omega == 0: BREAKDOWN, stop
+ *     tol > 0 and hist[0] > 0 and hist[k] / hist[0] < tol: stop
+ *     beta = (rho' / rho) (alpha / omega); rho' == 0 or beta not finite: BREAKDOWN, stop
+ *     p = r + beta (p - omega v); rho = rho'
+ * A breakdown is a status, not an error: the call returns AMG_OK, *status is
+ * AMG_KRYLOV_BREAKDOWN, x is the last iterate written (never a non-finite value from a failed
+ * quotient) and *iters the number of history entries minus one.  r = 0 at entry gives
+ * *iters = 0, hist = [0], BREAKDOWN and leaves x untouched.  hist: max_iter + 1 doubles.
+ * The scalars stay on the device: with tol == 0 nothing waits for the host inside the loop.
+ * max_iter < 0 or overlapping x, b: AMG_ERR_INVALID before any work. */
+#define AMG_KRYLOV_OK 0
+#define AMG_KRYLOV_BREAKDOWN 1
+int amg_solver_bicgstab(amg_solver S, double* x, const double* b, int32_t max_iter, double tol,
+                        double* hist, int32_t* iters, int32_t* status);
 /* Capture each V-cycle in a hipGraph and replay it (1 = on).  Default: on for 1 rank; off
  * for loopback ranks (they meet at host barriers); for RCCL ranks on where the process runs
  * the runtime whole-cycle capture was validated on (HIP >= 7.2 with RCCL >= 2.27.7: the

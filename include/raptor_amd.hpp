@@ -237,6 +237,17 @@ public:
         hist.resize((size_t)it + 1);
         return hist;
     }
+    // BiCGStab for nonsymmetric operators, right-preconditioned by one V-cycle (two cycles per
+    // iteration); *status (optional) gets AMG_KRYLOV_OK or AMG_KRYLOV_BREAKDOWN
+    std::vector<double> bicgstab(double* x, const double* b, int max_iter, double tol = 0.0,
+                                 int* status = nullptr) {
+        std::vector<double> hist((size_t)max_iter + 1);
+        int32_t it = 0, st = AMG_KRYLOV_OK;
+        check(amg_solver_bicgstab(h_, x, b, max_iter, tol, hist.data(), &it, &st));
+        hist.resize((size_t)it + 1);
+        if (status) *status = st;
+        return hist;
+    }
     amg_solver handle() const { return h_; }
 
 private:

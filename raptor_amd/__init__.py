@@ -38,6 +38,8 @@ from ._lib import (  # noqa: F401  (re-exported constants)
     AMG_COARSEN_SA,
     AMG_INTERP_CLASSICAL,
     AMG_INTERP_EXT_I,
+    AMG_KRYLOV_BREAKDOWN,
+    AMG_KRYLOV_OK,
     AMG_SMOOTH_CHEBYSHEV,
     AMG_SMOOTH_HYBRID_GS,
     AMG_SMOOTH_JACOBI,
@@ -747,6 +749,17 @@ class ParMultilevel:
         check(lib().amg_solver_pcg(self.h, _ptr(x), _ptr(b), int(max_iter), float(tol),
                                    hist.ctypes.data_as(C.POINTER(C.c_double)), C.byref(it)))
         return x, hist[: it.value + 1]
+
+    def bicgstab(self, x, b, max_iter=20, tol=0.0):
+        """BiCGStab for nonsymmetric operators, right-preconditioned by one V-cycle (two cycles
+        per iteration).  Returns ``(x, hist, status)``; ``status`` is ``AMG_KRYLOV_OK`` or
+        ``AMG_KRYLOV_BREAKDOWN`` (a breakdown is no error: ``x`` is the last iterate written)."""
+        hist = np.zeros(max(int(max_iter), 0) + 1)
+        it, st = C.c_int32(), C.c_int32()
+        check(lib().amg_solver_bicgstab(self.h, _ptr(x), _ptr(b), int(max_iter), float(tol),
+                                        hist.ctypes.data_as(C.POINTER(C.c_double)), C.byref(it),
+                                        C.byref(st)))
+        return x, hist[: it.value + 1], int(st.value)
 
     def _release(self):
         h = getattr(self, "h", None)

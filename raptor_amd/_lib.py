@@ -18,6 +18,7 @@ AMG_INTERP_CLASSICAL, AMG_INTERP_EXT_I = 0, 1
 AMG_PRESET_PMIS_JACOBI, AMG_PRESET_RS_JACOBI, AMG_PRESET_SA_HYBRID_GS = 0, 1, 2
 AMG_REORDER_RCM = 1
 AMG_FORMAT_AUTO, AMG_FORMAT_CSR, AMG_FORMAT_BLOCKS = 0, 1, 2
+AMG_KRYLOV_OK, AMG_KRYLOV_BREAKDOWN = 0, 1
 
 ERROR_NAMES = {1: "INVALID", 2: "HIP", 3: "RCCL", 4: "COMM", 5: "INTERNAL", 6: "NOMEM"}
 
@@ -155,6 +156,8 @@ SIGNATURES = {
     "amg_solver_cycle": (C.c_int, [_vp, _vp, _vp]),
     "amg_solver_solve": (C.c_int, [_vp, _vp, _vp, _i32, _f64, _pf64, C.POINTER(_i32)]),
     "amg_solver_pcg": (C.c_int, [_vp, _vp, _vp, _i32, _f64, _pf64, C.POINTER(_i32)]),
+    "amg_solver_bicgstab": (C.c_int, [_vp, _vp, _vp, _i32, _f64, _pf64, C.POINTER(_i32),
+                                      C.POINTER(_i32)]),
     "amg_solver_set_graph": (C.c_int, [_vp, _i32]),
     "amg_solver_get_graph": (C.c_int, [_vp, C.POINTER(_i32)]),
     "amg_solver_cycle_timeline": (C.c_int, [_vp, _vp, _vp, _i32, _i32, C.POINTER(C.c_double), C.c_char_p, _i32,

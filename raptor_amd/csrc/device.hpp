@@ -563,6 +563,30 @@ void launch_pcg_xr(hipStream_t s, int64_t n, const double* rz, const double* pq,
 void launch_pcg_p(hipStream_t s, int64_t n, const double* rz_new, const double* rz_old,
                   const double* z, double* p);
 void launch_append(hipStream_t s, const double* v, double* hist, int* counter);
+// BiCGStab helpers (Solver::bicgstab).  sc: the iteration's device scalar block; sc[BS_FLAG] is
+// the stop flag, set by the finishing launches and read by every vector kernel (a set flag makes
+// the kernel return at once).  `in`: per-rank sums, one (start, alpha) or two (omega, step) per
+// rank, added in rank order.
+enum { BS_RHO = 0, BS_ALPHA, BS_OMEGA, BS_BETA, BS_H0, BS_TOL, BS_FLAG, BS_N };
+constexpr double BICG_RUN = 0.0, BICG_BREAKDOWN = 1.0, BICG_CONVERGED = 2.0;
+void launch_bicg_start(hipStream_t s, int nr, const double* in, double* sc, double tol, double* hist,
+                       int* counter);
+void launch_bicg_alpha(hipStream_t s, int nr, const double* in, double* sc);
+void launch_bicg_omega(hipStream_t s, int nr, const double* in, double* sc);
+void launch_bicg_step(hipStream_t s, int nr, const double* in, double* sc, double* hist, int* counter);
+// s = r - alpha v
+void launch_bicg_s(hipStream_t s, int64_t n, const double* sc, const double* r, const double* v,
+                   double* sv);
+// p = r + beta (p - omega v)
+void launch_bicg_p(hipStream_t s, int64_t n, const double* sc, const double* r, const double* v,
+                   double* p);
+// dot_partials_kernel's partials of t.s and t.t in one pass
+void launch_bicg_tsdot(hipStream_t s, int64_t n, const double* sc, const double* t, const double* sv,
+                       double* part_ts, double* part_tt);
+// x = (x + alpha ph) + omega sh; r = sv - omega t; the partials of r.r and rhat.r
+void launch_bicg_xr(hipStream_t s, int64_t n, const double* sc, const double* ph, const double* sh,
+                    const double* sv, const double* t, const double* rhat, double* x, double* r,
+                    double* part_rr, double* part_rhr);
 // x_i = inv_i . b, one wavefront per row, lane-interleaved partial sums + xor butterfly
 void launch_dense_gemv(hipStream_t s, int64_t n_local, int64_t n, const double* inv,
                        const double* b, double* x);
@@ -643,10 +667,11 @@ struct Solver {
         const double* x = nullptr;
         const double* b = nullptr;
         int64_t fmt_gen = -1;
-    } graphs[5];  // [0] plain cycle, [1] cycle that also appends ||b - A x_in||, [2] the
+    } graphs[7];  // [0] plain cycle, [1] cycle that also appends ||b - A x_in||, [2] the
                   // residual norm alone (solve's last norm), [3] / [4] the two halves of a
-                  // PCG iteration (Solver::pcg)
-    enum { G_CYCLE = 0, G_CYCLE_NORM = 1, G_NORM = 2, G_PCG_STEP = 3, G_PCG_PREC = 4 };
+                  // PCG iteration (Solver::pcg), [5] / [6] those of a BiCGStab iteration
+    enum { G_CYCLE = 0, G_CYCLE_NORM = 1, G_NORM = 2, G_PCG_STEP = 3, G_PCG_PREC = 4,
+           G_BICG_S = 5, G_BICG_XR = 6 };
     // the graph in `slot` captured for (x, b) -- recaptured by `body` when stale.  Multi-rank
     // with `agree`: the ranks decide together (host allgather of the stale flags, then of the
     // capture / instantiate status), so no rank captures while a peer replays.  false: the
@@ -698,6 +723,12 @@ struct Solver {
     int32_t pcg(double* x, const double* b, int32_t max_iter, double tol, double* hist_host);
     DevBuf<double> pcg_vec, pcg_scratch;  // r | z | p | q ; dot partials | tmp | gathered | scalars
     void dot(const double* a, const double* b, double* dst, bool take_sqrt);
+    // V-cycle-preconditioned BiCGStab for nonsymmetric operators (right preconditioning,
+    // DESIGN.md 3); returns the iterations counted, *status gets AMG_KRYLOV_OK / _BREAKDOWN
+    int32_t bicgstab(double* x, const double* b, int32_t max_iter, double tol, double* hist_host,
+                     int32_t* status);
+    // r | rhat | p | v | s | t | phat | shat ; two partial arrays | tmp | gathered | local | scalars
+    DevBuf<double> bicg_vec, bicg_scratch;
     // in-graph time of every operation of a cycle (amg_solver_cycle_timeline, one rank): while
     // tl_on, cycle_rec marks the end of each operation -- a timing event when eager, the end of
     // a captured segment (one graph per operation, replayed back to back) when capturing

@@ -2257,6 +2257,180 @@ __global__ void append_kernel(const double* v, double* hist, int* counter) {
     }
 }
 
+// ---- BiCGStab vector kernels --------------------------------------------------
+// The scalars of the iteration live in one device block sc[BS_*] (device.hpp); sc[BS_FLAG] is
+// the stop flag.  Single-thread finishing launches form the next scalar from the rank sums of a
+// dot product (rank order, as finish_sum_kernel) and set the flag; every vector kernel returns at
+// once when it is set, so replays after a stop change nothing.
+__device__ __forceinline__ double rank_sum(int nr, const double* in, int stride) {
+    double s = 0.0;
+    for (int i = 0; i < nr; ++i) s += in[(size_t)i * stride];
+    return s;
+}
+
+// set-up: rr = r.r; rho = rr; hist[0] = sqrt(rr); flag cleared, tol stored for the step finish
+__global__ void bicg_start_kernel(int nr, const double* in, double* sc, double tol, double* hist,
+                                  int* counter) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double rr = rank_sum(nr, in, 1);
+    const double h = sqrt(rr);
+    sc[BS_RHO] = rr;
+    sc[BS_H0] = h;
+    sc[BS_TOL] = tol;
+    sc[BS_ALPHA] = sc[BS_OMEGA] = sc[BS_BETA] = 0.0;
+    sc[BS_FLAG] = BICG_RUN;
+    hist[*counter] = h;
+    *counter += 1;
+}
+
+// alpha = rho / (rhat . v); rv == 0 or a non-finite quotient is a breakdown
+__global__ void bicg_alpha_kernel(int nr, const double* in, double* sc) {
+    if (threadIdx.x != 0 || blockIdx.x != 0 || sc[BS_FLAG] != BICG_RUN) return;
+    const double rv = rank_sum(nr, in, 1);
+    const double alpha = sc[BS_RHO] / rv;
+    if (rv == 0.0 || !isfinite(alpha)) sc[BS_FLAG] = BICG_BREAKDOWN;
+    else sc[BS_ALPHA] = alpha;
+}
+
+// omega = (t . s) / (t . t) from in[2 rank], in[2 rank + 1]; tt == 0 or non-finite: omega = 0
+__global__ void bicg_omega_kernel(int nr, const double* in, double* sc) {
+    if (threadIdx.x != 0 || blockIdx.x != 0 || sc[BS_FLAG] != BICG_RUN) return;
+    const double ts = rank_sum(nr, in, 2);
+    const double tt = rank_sum(nr, in + 1, 2);
+    double omega = ts / tt;
+    if (tt == 0.0 || !isfinite(omega)) omega = 0.0;
+    sc[BS_OMEGA] = omega;
+}
+
+// after the x / r update: rr = r.r and rho' = rhat.r from in[2 rank], in[2 rank + 1];
+// hist gets sqrt(rr) (the iteration is counted), then the stopping rules in the definition's
+// order: omega == 0 (breakdown), the tolerance, beta's breakdown; else beta and rho for the next
+__global__ void bicg_step_kernel(int nr, const double* in, double* sc, double* hist, int* counter) {
+    if (threadIdx.x != 0 || blockIdx.x != 0 || sc[BS_FLAG] != BICG_RUN) return;
+    const double rr = rank_sum(nr, in, 2);
+    const double rho_new = rank_sum(nr, in + 1, 2);
+    const double h = sqrt(rr);
+    hist[*counter] = h;
+    *counter += 1;
+    const double omega = sc[BS_OMEGA], tol = sc[BS_TOL], h0 = sc[BS_H0];
+    if (omega == 0.0) {
+        sc[BS_FLAG] = BICG_BREAKDOWN;
+        return;
+    }
+    if (tol > 0.0 && h0 > 0.0 && h / h0 < tol) {
+        sc[BS_FLAG] = BICG_CONVERGED;
+        return;
+    }
+    const double beta = (rho_new / sc[BS_RHO]) * (sc[BS_ALPHA] / omega);
+    if (rho_new == 0.0 || !isfinite(beta)) {
+        sc[BS_FLAG] = BICG_BREAKDOWN;
+        return;
+    }
+    sc[BS_BETA] = beta;
+    sc[BS_RHO] = rho_new;
+}
+
+// s = r - alpha v
+__global__ void bicg_s_kernel(long long n, const double* sc, const double* r, const double* v,
+                              double* s) {
+    if (sc[BS_FLAG] != BICG_RUN) return;
+    const double alpha = sc[BS_ALPHA];
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) s[i] = r[i] - alpha * v[i];
+}
+
+// p = r + beta (p - omega v)
+__global__ void bicg_p_kernel(long long n, const double* sc, const double* r, const double* v,
+                              double* p) {
+    if (sc[BS_FLAG] != BICG_RUN) return;
+    const double beta = sc[BS_BETA], omega = sc[BS_OMEGA];
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) p[i] = r[i] + beta * (p[i] - omega * v[i]);
+}
+
+// dot_partials_kernel's block value of two per-lane sums at once (same tree for each)
+__device__ __forceinline__ void dot_block_tree2(double s0, double s1, double (*red)[kTPB / 64],
+                                                double* part0, double* part1) {
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, 64);
+        s1 += __shfl_down(s1, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = s0;
+        red[1][threadIdx.x >> 6] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part0[blockIdx.x] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+        part1[blockIdx.x] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    }
+}
+
+// the partials of t.s and t.t in one pass: dot_partials_kernel's mapping and sums exactly (block
+// g covers [g kDotSpan, (g+1) kDotSpan), lane t adds entries t + 256 j in order from 0.0)
+__global__ __launch_bounds__(kTPB) void bicg_tsdot_kernel(long long n, const double* sc,
+                                                          const double* t, const double* s,
+                                                          double* part_ts, double* part_tt) {
+    __shared__ double red[2][kTPB / 64];
+    if (sc[BS_FLAG] != BICG_RUN) return;  // grid-uniform
+    const long long base = (long long)blockIdx.x * kDotSpan + threadIdx.x;
+    double tv[8], sv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const long long i = base + (long long)j * kTPB;
+        tv[j] = i < n ? t[i] : 0.0;
+        sv[j] = i < n ? s[i] : 0.0;
+    }
+    double a = 0.0, c = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if (base + (long long)j * kTPB < n) {
+            a += tv[j] * sv[j];
+            c += tv[j] * tv[j];
+        }
+    }
+    dot_block_tree2(a, c, red, part_ts, part_tt);
+}
+
+// x = (x + alpha ph) + omega sh; r = s - omega t; the partials of r.r and rhat.r from the r just
+// formed, in dot_partials_kernel's mapping
+__global__ __launch_bounds__(kTPB) void bicg_xr_kernel(long long n, const double* sc, const double* ph,
+                                                       const double* sh, const double* s,
+                                                       const double* t, const double* rhat, double* x,
+                                                       double* r, double* part_rr, double* part_rhr) {
+    __shared__ double red[2][kTPB / 64];
+    if (sc[BS_FLAG] != BICG_RUN) return;  // grid-uniform
+    const double alpha = sc[BS_ALPHA], omega = sc[BS_OMEGA];
+    const long long base = (long long)blockIdx.x * kDotSpan + threadIdx.x;
+    double xv[8], pv[8], hv[8], sv[8], tv[8], qv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const long long i = base + (long long)j * kTPB;
+        const bool in = i < n;
+        xv[j] = in ? x[i] : 0.0;
+        pv[j] = in ? ph[i] : 0.0;
+        hv[j] = in ? sh[i] : 0.0;
+        sv[j] = in ? s[i] : 0.0;
+        tv[j] = in ? t[i] : 0.0;
+        qv[j] = in ? rhat[i] : 0.0;
+    }
+    double a = 0.0, c = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const long long i = base + (long long)j * kTPB;
+        if (i < n) {
+            const double rn = sv[j] - omega * tv[j];
+            x[i] = (xv[j] + alpha * pv[j]) + omega * hv[j];
+            r[i] = rn;
+            a += rn * rn;
+            c += qv[j] * rn;
+        }
+    }
+    dot_block_tree2(a, c, red, part_rr, part_rhr);
+}
+
 }  // namespace
 
 int dot_partial_count(int64_t n) { return (int)std::max<int64_t>(1, (n + kDotSpan - 1) / kDotSpan); }
@@ -2283,6 +2457,57 @@ void launch_pcg_p(hipStream_t s, int64_t n, const double* rz_new, const double* 
                   const double* z, double* p) {
     if (n <= 0) return;
     hipLaunchKernelGGL(pcg_p_kernel, dim3(grid_for(n)), dim3(kTPB), 0, s, (long long)n, rz_new, rz_old, z, p);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_bicg_start(hipStream_t s, int nr, const double* in, double* sc, double tol, double* hist,
+                       int* counter) {
+    hipLaunchKernelGGL(bicg_start_kernel, dim3(1), dim3(64), 0, s, nr, in, sc, tol, hist, counter);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_bicg_alpha(hipStream_t s, int nr, const double* in, double* sc) {
+    hipLaunchKernelGGL(bicg_alpha_kernel, dim3(1), dim3(64), 0, s, nr, in, sc);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_bicg_omega(hipStream_t s, int nr, const double* in, double* sc) {
+    hipLaunchKernelGGL(bicg_omega_kernel, dim3(1), dim3(64), 0, s, nr, in, sc);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_bicg_step(hipStream_t s, int nr, const double* in, double* sc, double* hist, int* counter) {
+    hipLaunchKernelGGL(bicg_step_kernel, dim3(1), dim3(64), 0, s, nr, in, sc, hist, counter);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_bicg_s(hipStream_t s, int64_t n, const double* sc, const double* r, const double* v,
+                   double* sv) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(bicg_s_kernel, dim3(grid_for(n)), dim3(kTPB), 0, s, (long long)n, sc, r, v, sv);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_bicg_p(hipStream_t s, int64_t n, const double* sc, const double* r, const double* v,
+                   double* p) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(bicg_p_kernel, dim3(grid_for(n)), dim3(kTPB), 0, s, (long long)n, sc, r, v, p);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_bicg_tsdot(hipStream_t s, int64_t n, const double* sc, const double* t, const double* sv,
+                       double* part_ts, double* part_tt) {
+    const int g = dot_partial_count(n);
+    hipLaunchKernelGGL(bicg_tsdot_kernel, dim3(g), dim3(kTPB), 0, s, (long long)n, sc, t, sv, part_ts, part_tt);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_bicg_xr(hipStream_t s, int64_t n, const double* sc, const double* ph, const double* sh,
+                    const double* sv, const double* t, const double* rhat, double* x, double* r,
+                    double* part_rr, double* part_rhr) {
+    const int g = dot_partial_count(n);
+    hipLaunchKernelGGL(bicg_xr_kernel, dim3(g), dim3(kTPB), 0, s, (long long)n, sc, ph, sh, sv, t, rhat,
+                       x, r, part_rr, part_rhr);
     HIP_CHECK(hipGetLastError());
 }
 

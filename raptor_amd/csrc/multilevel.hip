@@ -1316,6 +1316,119 @@ int32_t Solver::pcg(double* x, const double* b, int32_t max_iter, double tol, do
     return it;
 }
 
+// ---- AMG-preconditioned BiCGStab --------------------------------------------
+// Right-preconditioned BiCGStab for nonsymmetric operators, M = one V-cycle from zero.  alpha,
+// omega, beta, rho, the stop flag and the history counter stay on the device: single-thread
+// finishing launches form them after each dot product, and every vector kernel of the iteration
+// returns at once when the flag is set, so with tol == 0 the loop never waits for the host and
+// the replays after a breakdown change nothing.  With graphs on an iteration is two captured
+// graphs, as in pcg: G_BICG_S (phat = M p, v = A phat, rhat.v, alpha, s) and G_BICG_XR (shat =
+// M s, t = A shat, t.s and t.t, omega, the x / r update with r.r and rhat.r, beta, p).
+int32_t Solver::bicgstab(double* x, const double* b, int32_t max_iter, double tol, double* hist_host,
+                         int32_t* status) {
+    AMG_CHECK(max_iter >= 0, "max_iter must be >= 0");
+    RoctxRange range("ParMultilevel::bicgstab");
+    DevMatrix& A = *A0;
+    const int64_t n = A.n_rows;
+    hipStream_t s = ctx->stream;
+    const int nr = ctx->host.nranks;
+    const int g = dot_partial_count(n);
+    const size_t ntmp = (size_t)g / 4096 + 64;
+    const size_t need = 2 * (size_t)g + ntmp + 2 * (size_t)nr + 2 + BS_N;
+    if (bicg_vec.n < (size_t)(8 * n + 8) || bicg_scratch.n < need) {
+        // the captured iteration graphs hold these addresses
+        drop_graph(graphs[G_BICG_S]);
+        drop_graph(graphs[G_BICG_XR]);
+        if (bicg_vec.n < (size_t)(8 * n + 8)) bicg_vec.alloc((size_t)(8 * n + 8));
+        if (bicg_scratch.n < need) {
+            bicg_scratch.alloc(need);
+            // after a stop the gated kernels leave the partials unwritten and the reductions
+            // still read them
+            HIP_CHECK(hipMemsetAsync(bicg_scratch.p, 0, need * sizeof(double), s));
+        }
+    }
+    double* r = bicg_vec.p;
+    double* rhat = r + n;
+    double* p = rhat + n;
+    double* v = p + n;
+    double* sv = v + n;
+    double* t = sv + n;
+    double* ph = t + n;
+    double* sh = ph + n;
+    double* part0 = bicg_scratch.p;
+    double* part1 = part0 + g;
+    double* tmp = part1 + g;
+    double* gathered = tmp + ntmp;
+    double* local = gathered + 2 * (size_t)nr;
+    double* sc = local + 2;
+    ensure_hist(max_iter + 1);
+    if (nr > 1) ctx->eager_rccl_fence();  // replays of earlier calls
+    HIP_CHECK(hipMemsetAsync(hist_counter.p, 0, sizeof(int), s));
+    // the rank sums of `count` dot products whose partials sit in part0 (and part1): one
+    // reduction each, one allgather of `count` values per rank
+    auto rank_sums = [&](int count) -> const double* {
+        launch_reduce_partials(s, g, part0, tmp, local);
+        if (count == 2) launch_reduce_partials(s, g, part1, tmp, local + 1);
+        if (nr == 1) return local;
+        ctx->allgather(local, gathered, (size_t)count);
+        return gathered;
+    };
+    auto apply_m = [&](const double* in, double* out) {  // out = M(in): one V-cycle from zero
+        launch_zero(s, n, out);
+        cycle_rec(0, out, in, false, false);
+    };
+    auto first = [&] {  // phat = M p; v = A phat; alpha = rho / rhat.v; s = r - alpha v
+        apply_m(p, ph);
+        par_apply(A, KM_SPMV, ph, nullptr, v, 0.0, nullptr);
+        launch_dot_partials(s, n, rhat, v, part0);
+        launch_bicg_alpha(s, nr, rank_sums(1), sc);
+        launch_bicg_s(s, n, sc, r, v, sv);
+    };
+    auto second = [&] {  // shat = M s; t = A shat; omega; x, r; ||r|| appended; beta; p
+        apply_m(sv, sh);
+        par_apply(A, KM_SPMV, sh, nullptr, t, 0.0, nullptr);
+        launch_bicg_tsdot(s, n, sc, t, sv, part0, part1);
+        launch_bicg_omega(s, nr, rank_sums(2), sc);
+        launch_bicg_xr(s, n, sc, ph, sh, sv, t, rhat, x, r, part0, part1);
+        launch_bicg_step(s, nr, rank_sums(2), sc, hist.p, hist_counter.p);
+        launch_bicg_p(s, n, sc, r, v, p);
+    };
+    par_apply(A, KM_RESID, x, b, r, 0.0, nullptr);
+    if (n) {
+        HIP_CHECK(hipMemcpyAsync(rhat, r, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(p, r, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    launch_dot_partials(s, n, r, r, part0);
+    launch_bicg_start(s, nr, rank_sums(1), sc, tol, hist.p, hist_counter.p);
+    // one collective graph decision for both iteration graphs (keyed by the caller's x, b)
+    agree_stale({G_BICG_S, G_BICG_XR}, x, b);
+    auto run = [&](int slot, const std::function<void()>& body) {
+        if (use_graph && graph_ready(slot, x, b, body, false)) graph_launch(slot);
+        else body();
+    };
+    double flag = BICG_RUN;
+    for (int32_t it = 0; it < max_iter; ++it) {
+        run(G_BICG_S, first);
+        run(G_BICG_XR, second);
+        if (tol > 0.0) {  // the device applied the stopping rules: the host only learns of it
+            HIP_CHECK(hipMemcpyAsync(&flag, sc + BS_FLAG, sizeof(double), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            ctx->graph_inflight = false;
+            if (flag != BICG_RUN) break;
+        }
+    }
+    int count = 0;
+    HIP_CHECK(hipMemcpyAsync(&count, hist_counter.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&flag, sc + BS_FLAG, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    ctx->graph_inflight = false;
+    AMG_ASSERT(count >= 1 && count <= max_iter + 1);
+    HIP_CHECK(hipMemcpyAsync(hist_host, hist.p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    *status = flag == BICG_BREAKDOWN ? AMG_KRYLOV_BREAKDOWN : AMG_KRYLOV_OK;
+    return count - 1;
+}
+
 static int64_t spmv_bytes(const DevMatrix& M) {
     // a segment row map is one more index stream of the operator: 4 B per segment
     const int64_t map = M.row_seg > 0 ? 4 * (M.n_rows / M.row_seg) : 0;
