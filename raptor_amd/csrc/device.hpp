@@ -593,6 +593,20 @@ void launch_dense_gemv(hipStream_t s, int64_t n_local, int64_t n, const double* 
 void launch_uniform(hipStream_t s, int64_t n, int64_t first_gid, uint64_t seed, double* out);
 void launch_zero(hipStream_t s, int64_t n, double* y);
 
+// the largest |v_i|: non-negative doubles order like their bit patterns, so an integer atomicMax
+// is exact in any order
+__device__ __forceinline__ void dmax_abs(unsigned long long* m, double v) {
+    atomicMax(m, (unsigned long long)__double_as_longlong(fabs(v)));
+}
+// The max-norm power iteration DESIGN.md 3 defines for SA's rho (setup_device.hip; also the
+// Chebyshev lambda_l): x = u / max|u|, u the seeded uniform vector of the global ids first_gid + i;
+// `iters` times: step(m) writes one step's y from x and atomically maxes |y_i| into the zeroed
+// word m (dmax_abs), lambda = max|y| over all ranks (dist) -- exact in any order, so the same
+// on every partition --, x = y / lambda; stops at lambda = 0.  Returns the last lambda.  x, y:
+// n device doubles.  Collective when dist: every rank calls it, rows or not.
+double power_iteration(hipStream_t s, const HostComm& comm, bool dist, int n, int64_t first_gid, uint64_t seed,
+                       int iters, double* x, const double* y, const std::function<void(unsigned long long* m)>& step);
+
 // ParCSRMatrix operations with halo exchange + interior/boundary overlap
 // KM_CHEBY: omega = c2, xprev (null: zeros; y may alias it, y must not alias x) and c1
 void par_apply(DevMatrix& A, int mode, const double* x, const double* b, double* y, double omega,

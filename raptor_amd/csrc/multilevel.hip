@@ -537,43 +537,24 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
 namespace {
 constexpr int kChebyEigIters = 10;  // power steps of lambda_l (SA's rho: DESIGN.md 3)
 
-// the largest |v_i|: non-negative doubles order like their bit patterns, so an integer atomicMax
-// is exact in any order
-__device__ __forceinline__ void eig_max_abs(unsigned long long* m, double v) {
-    atomicMax(m, (unsigned long long)__double_as_longlong(fabs(v)));
-}
-
-__global__ __launch_bounds__(kTPB) void eig_max_kernel(int n, const double* x, unsigned long long* m) {
-    const int i = blockIdx.x * kTPB + threadIdx.x;
-    if (i < n) eig_max_abs(m, x[i]);
-}
-
-__global__ __launch_bounds__(kTPB) void eig_scale_kernel(int n, const double* y, double lam, double* x) {
-    const int i = blockIdx.x * kTPB + threadIdx.x;
-    if (i < n) x[i] = y[i] / lam;
-}
-
 // y_i = (A x)_i / a_ii (the division by the diagonal itself) and max |y_i|
 __global__ __launch_bounds__(kTPB) void eig_div_max_kernel(int n, const double* d, double* y, unsigned long long* m) {
     const int i = blockIdx.x * kTPB + threadIdx.x;
     if (i >= n) return;
     const double v = y[i] / d[i];
     y[i] = v;
-    eig_max_abs(m, v);
+    dmax_abs(m, v);
 }
 }  // namespace
 
 // lambda_l = rho(D^-1 A_l) of every level but the coarsest by the power iteration DESIGN.md 3
-// defines for SA's rho, on A_l itself: x = u / max|u|, u the seeded uniform vector of the global
-// ids (seed + l); 10 times y = (A x) / a_ii, lambda = max|y| (exact in any order, so the same on
-// every partition), x = y / lambda; stop at lambda = 0.  Then the coefficients, on the host in
-// the order the definition writes them.
+// defines for SA's rho (power_iteration, setup_device.hip), on A_l itself: the seeded vector of
+// the global ids (seed + l), kChebyEigIters times y = (A x) / a_ii.  Then the coefficients, on the
+// host in the order the definition writes them.
 void Solver::setup_cheby() {
     const HostComm& comm = ctx->host;
     hipStream_t s = ctx->stream;
     cheby.assign(levels.size(), Cheby{});
-    DevBuf<unsigned long long> mx;
-    mx.alloc(1);
     for (size_t l = 0; l + 1 < levels.size(); ++l) {
         DevMatrix& A = Amat(l);
         A.ensure_built();
@@ -591,29 +572,12 @@ void Solver::setup_cheby() {
         d.upload(dh.data(), dh.size());
         double* x = levels[l].r.p;  // the level's work vectors: free until the first cycle
         double* y = levels[l].t.p;
-        auto global_max = [&]() {
-            unsigned long long bits = 0;
-            HIP_CHECK(hipMemcpyAsync(&bits, mx.p, sizeof(bits), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            double m;
-            std::memcpy(&m, &bits, sizeof(m));
-            return dist ? comm.allreduce_max(m) : m;
-        };
-        launch_uniform(s, n, A.first_row, opt.seed + (uint64_t)l, x);
-        HIP_CHECK(hipMemsetAsync(mx.p, 0, sizeof(unsigned long long), s));
-        if (n) hipLaunchKernelGGL(eig_max_kernel, dim3(g), dim3(kTPB), 0, s, n, x, mx.p);
-        const double m0 = global_max();
-        if (m0 > 0.0 && n) hipLaunchKernelGGL(eig_scale_kernel, dim3(g), dim3(kTPB), 0, s, n, x, m0, x);
-        double lam = 0.0;
-        for (int it = 0; it < kChebyEigIters; ++it) {
+        auto step = [&](unsigned long long* mx) {  // y = (A x) / a_ii, max |y_i| into mx
             par_apply(A, KM_SPMV, x, nullptr, y, 0.0, nullptr);
-            HIP_CHECK(hipMemsetAsync(mx.p, 0, sizeof(unsigned long long), s));
-            if (n) hipLaunchKernelGGL(eig_div_max_kernel, dim3(g), dim3(kTPB), 0, s, n, d.p, y, mx.p);
-            HIP_CHECK(hipGetLastError());
-            lam = global_max();
-            if (lam == 0.0) break;
-            if (n) hipLaunchKernelGGL(eig_scale_kernel, dim3(g), dim3(kTPB), 0, s, n, y, lam, x);
-        }
+            if (n) hipLaunchKernelGGL(eig_div_max_kernel, dim3(g), dim3(kTPB), 0, s, n, d.p, y, mx);
+        };
+        const double lam =
+            power_iteration(s, comm, dist, n, A.first_row, opt.seed + (uint64_t)l, kChebyEigIters, x, y, step);
         HIP_CHECK(hipStreamSynchronize(s));  // d is freed here
         Cheby& c = cheby[l];
         const int m = opt.cheby_degree;

@@ -16,6 +16,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "device.hpp"
 
@@ -404,10 +405,6 @@ __global__ void interp_kernel(ARows R, DCsr S, const int* cf, const int* hcf, co
 // Rows longer than kIwMax entries run interp_kernel's loops on lane 0.
 constexpr int kIwWaves = 4, kIwMax = 512;
 enum { IW_STRONG = 1, IW_C = 2, IW_DIAG = 4, IW_POS = 8 };
-
-template <bool FILL>
-__device__ void interp_row_serial(const ARows& R, const DCsr& S, const int* cf, const int* hcf, const int* cmap,
-                                  const int* hcmap, int* cnt, const int* prp, int* pcol, double* pval, int i);
 
 template <bool FILL>
 __global__ __launch_bounds__(64 * kIwWaves) void interp_wave_kernel(ARows R, DCsr S, const int* cf, const int* hcf,
@@ -962,12 +959,6 @@ __global__ void sa_filter_kernel(DCsr A, Dist D, const double* d, const double* 
     }
 }
 
-// the largest |v_i|: non-negative doubles order like their bit patterns, so an integer
-// atomicMax is exact in any order
-__device__ __forceinline__ void dmax_abs(unsigned long long* m, double v) {
-    atomicMax(m, (unsigned long long)__double_as_longlong(fabs(v)));
-}
-
 __global__ void max_abs_kernel(int n, const double* __restrict__ x, unsigned long long* m) {
     const int i = blockIdx.x * kT + threadIdx.x;
     if (i < n) dmax_abs(m, x[i]);
@@ -1132,27 +1123,38 @@ __global__ void owner_bounds_kernel(int m, const int* __restrict__ keys, int nb,
 }
 
 // ---- helpers ---------------------------------------------------------------------------
-// exclusive scan of n ints into out[0..n] (out[n] = total)
-int64_t exclusive_scan(hipStream_t s, const int* in, int* out, int n, DevBuf<char>& tmp) {
-    size_t bytes = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n + 1, s));
-    if (tmp.n < bytes) tmp.alloc(bytes);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, in, out, n + 1, s));
-    int total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, out + n, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return total;
+// one thread per row.  Nothing is launched for n == 0 -- only the launch is skipped: a rank
+// without rows still makes every collective call around it
+template <class K, class... Args>
+void launch_rows(hipStream_t s, long long n, K kernel, Args... args) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(kernel, dim3(grid1(n)), dim3(kT), 0, s, args...);
+    HIP_CHECK(hipGetLastError());
 }
 
-int64_t exclusive_scan64(hipStream_t s, const long long* in, long long* out, int n, DevBuf<char>& tmp) {
+// one device word, once the stream has produced it
+template <class T>
+T read_scalar(hipStream_t s, const T* dev) {
+    T v{};
+    HIP_CHECK(hipMemcpyAsync(&v, dev, sizeof(T), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    return v;
+}
+
+// exclusive scan of n ints / long longs into out[0..n]; returns out[n], the total
+template <class I>
+int64_t exclusive_scan(hipStream_t s, const I* in, I* out, int n, DevBuf<char>& tmp) {
     size_t bytes = 0;
     HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, n + 1, s));
     if (tmp.n < bytes) tmp.alloc(bytes);
     HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, bytes, in, out, n + 1, s));
-    long long total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, out + n, sizeof(long long), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    return total;
+    return read_scalar(s, out + n);
+}
+
+std::vector<int32_t> download_ints(hipStream_t s, const int* p, int64_t n) {
+    std::vector<int32_t> h((size_t)n);
+    copy_to_host(h.data(), p, sizeof(int) * n, s);
+    return h;
 }
 
 // index-width conversions of the setup's device images (grid-stride: up to 2^31 entries)
@@ -1167,44 +1169,6 @@ __global__ void widen_kernel(long long n, const int* __restrict__ in, long long*
 }
 
 inline unsigned grid_cap(long long n) { return std::min<unsigned>(grid1(n), 1u << 16); }
-
-// P = T - (omega / a_ii) A T on the device, rows merged by column exactly as the host merge in
-// level_setup_device (sa_prolongator): T has one entry per row (aggregate agg_i, value t_i)
-template <bool FILL>
-__global__ void sa_smooth_kernel(int n, const long long* __restrict__ atrp, const long long* __restrict__ atcol,
-                                 const double* __restrict__ atval, const long long* __restrict__ agg,
-                                 const double* __restrict__ tval, const double* __restrict__ d, double omega,
-                                 long long* __restrict__ cnt, const long long* __restrict__ prp,
-                                 long long* __restrict__ pcol, double* __restrict__ pval) {
-    const int i = blockIdx.x * kT + threadIdx.x;
-    if (i >= n) return;
-    const long long b = atrp[i], e = atrp[i + 1], jt = agg[i];
-    if (!FILL) {
-        long long lo = b, hi = e;
-        while (lo < hi) {
-            const long long m = (lo + hi) >> 1;
-            if (atcol[m] < jt) lo = m + 1;
-            else hi = m;
-        }
-        cnt[i] = (e - b) + ((lo < e && atcol[lo] == jt) ? 0 : 1);
-        return;
-    }
-    const double c = omega * (1.0 / d[i]);
-    long long ka = b, q = prp[i];
-    bool tleft = true;
-    while (ka < e || tleft) {
-        const long long ja = ka < e ? atcol[ka] : LLONG_MAX, jj = tleft ? jt : LLONG_MAX;
-        const long long j = ja < jj ? ja : jj;
-        double tvv = 0.0, av = 0.0;
-        if (jj == j) {
-            tvv = tval[i];
-            tleft = false;
-        }
-        if (ja == j) av = atval[ka++];
-        pcol[q] = j;
-        pval[q++] = tvv - c * av;
-    }
-}
 
 }  // namespace
 
@@ -1333,8 +1297,6 @@ __global__ void sp_rows_kernel(long long n, const long long* __restrict__ rp, co
     }
 }
 
-std::vector<int32_t> download_ints(hipStream_t s, const int* p, int64_t n);
-
 }  // namespace
 
 HostCSR sparsify_device(Context& ctx, const HostComm& comm, const HostCSR& A, double tau, SetupImages* imgs) {
@@ -1385,81 +1347,97 @@ HostCSR sparsify_device(Context& ctx, const HostComm& comm, const HostCSR& A, do
 
 namespace {
 
-// the level operator on the device: this rank's rows, global column ids (int32)
-struct DevLevel {
-    DevBuf<int> rp, col;
-    DevBuf<double> val;
-    int n = 0, lo = 0;
-    DCsr view() const { return DCsr{rp.p, col.p, val.p, n, lo}; }
+// Setup state that is built in place and passed by reference, never copied or moved: the
+// kernels' argument structs (Dist, ARows, ExtArgs) hold raw pointers into these buffers, and
+// later stages keep pointers to the plans and ghost rows
+struct Pinned {
+    Pinned() = default;
+    Pinned(const Pinned&) = delete;
+    Pinned& operator=(const Pinned&) = delete;
 };
 
-void upload_level(const HostComm& comm, const HostCSR& A, DevLevel& D) {
-    const int64_t n = A.nrows(), nnz = A.nnz();
-    AMG_CHECK(n < INT_MAX && nnz < INT_MAX && A.n_global_cols < INT_MAX,
-              "device setup: level exceeds int32 indexing");
-    std::vector<int> rp(n + 1), col((size_t)std::max<int64_t>(nnz, 1));
-#pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i <= n; ++i) rp[i] = (int)A.rp[i];
-#pragma omp parallel for schedule(static)
-    for (int64_t k = 0; k < nnz; ++k) col[k] = (int)A.col[k];
-    D.n = (int)n;
-    D.lo = (int)A.row_starts[comm.rank];
-    D.rp.upload(rp.data(), rp.size());
-    D.col.upload(col.data(), col.size());
-    if (nnz) D.val.upload(A.val.data(), (size_t)nnz);
-    else D.val.alloc(1);
-}
+// what every stage of one level reads: this rank's rows of A on the host and on the device
+struct LevelCtx : Pinned {
+    hipStream_t s;
+    const HostComm& comm;
+    const HostCSR& A;
+    const amg_options& opt;
+    const int level, n, lo;
+    const bool dist;
+    PhaseTimer tm;
+    DCsr Av{};          // A's device image (int32 rows, global column ids)
+    DevBuf<char> tmp;   // the scans' scratch
+    LevelCtx(hipStream_t stream, const HostComm& c, const HostCSR& Ah, const amg_options& o, int l)
+        : s(stream), comm(c), A(Ah), opt(o), level(l), n((int)Ah.nrows()), lo((int)Ah.row_starts[c.rank]),
+          dist(c.nranks > 1), tm(c) {}
+    uint64_t seed() const { return opt.seed + (uint64_t)level; }
+};
 
-struct DevS {  // strength graph / SA's filtered operator (this rank's rows, global column ids)
-    DevBuf<int> rp, col;
+// CSR rows built on the device by a count and a fill pass: the strength graph, SA's filtered
+// operator (int, global column ids) and P (int: PMIS, long long: SA)
+template <class I>
+struct DevRows : Pinned {
+    DevBuf<I> rp, col;
     DevBuf<double> val;
-    int n = 0, lo = 0;
     int64_t nnz = 0;
-    DCsr view() const { return DCsr{rp.p, col.p, val.p, n, lo}; }
 };
+using DevS = DevRows<int>;
+DCsr view(const LevelCtx& L, const DevS& M) { return DCsr{M.rp.p, M.col.p, M.val.p, L.n, L.lo}; }
 
-template <class CountK, class FillK>
-void build_strength(hipStream_t s, int n, int lo, DevS& S, DevBuf<char>& tmp, CountK count, FillK fill) {
-    DevBuf<int> cnt;
+// count(cnt) writes a count per row, the exclusive scan of the counts is rp[0..n], fill(rp, total)
+// allocates what it fills from the total and writes each row at its offset; returns the total
+template <class I, class CountK, class FillK>
+int64_t count_scan_fill(hipStream_t s, int n, DevBuf<I>& rp, DevBuf<char>& tmp, CountK count, FillK fill) {
+    DevBuf<I> cnt;
     cnt.alloc((size_t)n + 1);
-    HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(int) * cnt.n, s));
+    HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(I) * cnt.n, s));
     count(cnt.p);
-    S.rp.alloc((size_t)n + 1);
-    const int64_t nnz = exclusive_scan(s, cnt.p, S.rp.p, n, tmp);
-    S.nnz = nnz;
-    S.col.alloc((size_t)std::max<int64_t>(nnz, 1));
-    S.val.alloc((size_t)std::max<int64_t>(nnz, 1));
-    S.n = n;
-    S.lo = lo;
-    fill(S.rp.p, S.col.p, S.val.p);
+    rp.alloc((size_t)n + 1);
+    const int64_t total = exclusive_scan(s, cnt.p, rp.p, n, tmp);
+    fill(rp.p, total);
     HIP_CHECK(hipGetLastError());
+    return total;
 }
 
-std::vector<int32_t> download_ints(hipStream_t s, const int* p, int64_t n) {
-    std::vector<int32_t> h((size_t)n);
-    copy_to_host(h.data(), p, sizeof(int) * n, s);
-    return h;
+// the same for CSR rows: fill(rp, col, val)
+template <class I, class CountK, class FillK>
+void build_rows_with(LevelCtx& L, DevRows<I>& M, CountK count, FillK fill) {
+    M.nnz = count_scan_fill(L.s, L.n, M.rp, L.tmp, count, [&](const I* rp, int64_t nnz) {
+        M.col.alloc((size_t)std::max<int64_t>(nnz, 1));
+        M.val.alloc((size_t)std::max<int64_t>(nnz, 1));
+        fill(rp, M.col.p, M.val.p);
+    });
 }
 
-// A halo on the device: the sorted global ids (Dist lookups), the local send indices, and
-// forward(): pack on the device, the setup exchange on the host, the halo values uploaded
-struct DevHalo {
-    const HaloPlan* plan = nullptr;
+// ... by a thread-per-row kernel pair K<false> (counts) / K<true> (fills) whose parameters are
+// lead..., then (cnt, rp, col, val)
+template <class I, class KC, class KF, class... Lead>
+void build_rows(LevelCtx& L, DevRows<I>& M, KC count_k, KF fill_k, Lead... lead) {
+    build_rows_with(
+        L, M, [&](I* cnt) { launch_rows(L.s, L.n, count_k, lead..., cnt, nullptr, nullptr, nullptr); },
+        [&](const I* rp, I* col, double* val) { launch_rows(L.s, L.n, fill_k, lead..., nullptr, rp, col, val); });
+}
+
+// A halo on the device: its plan, the sorted global ids (Dist lookups), the local send indices,
+// and forward(): pack on the device, the setup exchange on the host, the halo values uploaded.
+// forward() is collective: every rank of a distributed level calls it, rows or not
+struct DevHalo : Pinned {
+    HaloPlan plan;
     DevBuf<int> gid, sidx;
-    void build(const HaloPlan& p) {
-        plan = &p;
-        std::vector<int> g(p.halo_gid.begin(), p.halo_gid.end()), si(p.send_idx.begin(), p.send_idx.end());
+    void build(HaloPlan p) {
+        plan = std::move(p);
+        std::vector<int> g(plan.halo_gid.begin(), plan.halo_gid.end()), si(plan.send_idx.begin(), plan.send_idx.end());
         gid.upload(g.data(), g.size());
         sidx.upload(si.data(), si.size());
     }
-    Dist dist(int lo, int n) const { return Dist{lo, n, gid.p, (int)plan->n_halo()}; }
+    Dist dist(int lo, int n) const { return Dist{lo, n, gid.p, (int)plan.n_halo()}; }
     template <class T>
     void forward(hipStream_t s, const HostComm& comm, const T* local, DevBuf<T>& halo) const {
-        const HaloPlan& p = *plan;
+        const HaloPlan& p = plan;
         const int ns = (int)p.send_idx.size();
         DevBuf<T> packed;
         packed.alloc((size_t)std::max(ns, 1));
-        if (ns) hipLaunchKernelGGL(pack_kernel_t<T>, dim3(grid1(ns)), dim3(kT), 0, s, ns, sidx.p, local, packed.p);
+        launch_rows(s, ns, pack_kernel_t<T>, ns, sidx.p, local, packed.p);
         std::vector<T> sbuf((size_t)ns), rbuf((size_t)p.n_halo());
         if (ns) HIP_CHECK(hipMemcpyAsync(sbuf.data(), packed.p, sizeof(T) * ns, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
@@ -1484,12 +1462,11 @@ constexpr int64_t kExtScratchInts = int64_t(1) << 26;  // 256 MiB of hash slots 
 constexpr int kExtLaunchRows = 1 << 18;                // rows (wavefronts) per interp_ext_kernel launch
 static_assert(kExtLaunchRows % kExtWaves == 0, "a launch covers whole workgroups of rows");
 
-struct ExtInterp {
+struct ExtInterp : Pinned {
     hipStream_t s = nullptr;
-    const HostCSR* A = nullptr;
+    const HostCSR* A = nullptr;  // A, its halo plan and ghost rows: the level's, which outlive this
     const HaloPlan* aplan = nullptr;
     const GhostRows* G = nullptr;
-    HaloPlan splan;
     DevHalo SH;
     DevBuf<int> scf, scmap, olist, on, err, iscr;
     DevBuf<unsigned char> ovf, bscr;
@@ -1500,12 +1477,10 @@ struct ExtInterp {
     std::vector<ExtSlot> slots;   // the rows of the scratch path
 
     void init(hipStream_t stream, const HostComm& comm, const HostCSR& Ah, const HaloPlan& ap, const GhostRows& Gh,
-              const ARows& Ar, const DCsr& Sv, const int* cf, const int* cmap, int ncg, const amg_options& opt,
-              int* pcnt) {
+              const ARows& Ar, const DCsr& Sv, const int* cf, const int* cmap, int ncg, const amg_options& opt) {
         s = stream, A = &Ah, aplan = &ap, G = &Gh;
         n = Ar.A.n, lo = Ar.A.lo, nc_global = ncg;
-        if (comm.nranks > 1) splan = ext_state_plan(comm, Ah, ap, Gh);
-        SH.build(splan);
+        SH.build(comm.nranks > 1 ? ext_state_plan(comm, Ah, ap, Gh) : HaloPlan());
         scf.alloc(1);
         scmap.alloc(1);
         if (comm.nranks > 1) {
@@ -1523,7 +1498,7 @@ struct ExtInterp {
         a.R = Ar, a.S = Sv, a.D2 = SH.dist(lo, n);
         a.cf = cf, a.hcf = scf.p, a.cmap = cmap, a.hcmap = scmap.p;
         a.theta = opt.strong_threshold, a.p_max = opt.p_max;
-        a.cnt = pcnt, a.prp = nullptr, a.pcol = nullptr, a.pval = nullptr;
+        a.cnt = nullptr, a.prp = nullptr, a.pcol = nullptr, a.pval = nullptr;
         a.ovf = ovf.p, a.ovf_list = olist.p, a.ovf_n = on.p, a.err = err.p;
     }
 
@@ -1536,9 +1511,7 @@ struct ExtInterp {
 
     // the listed rows' tables: |C^_i| <= min(sum of the row lengths of row i's columns, all C)
     void plan_slots() {
-        int no = 0;
-        HIP_CHECK(hipMemcpyAsync(&no, on.p, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
+        const int no = read_scalar(s, on.p);
         if (!no) return;
         std::vector<int32_t> rows = download_ints(s, olist.p, no);
         std::sort(rows.begin(), rows.end());
@@ -1584,7 +1557,7 @@ struct ExtInterp {
     // on (7-pt 512^3 on one rank), so the rows go in launches of kExtLaunchRows (as spgemm.hip
     // chunks its row kernels); returns the number of launches
     template <bool FILL>
-    int launch_rows() {
+    int launch_waves() {
         int launches = 0;
         for (int64_t r0 = 0; r0 < n; r0 += kExtLaunchRows, ++launches) {
             const int rows = (int)std::min<int64_t>(kExtLaunchRows, n - r0);
@@ -1597,374 +1570,397 @@ struct ExtInterp {
         return launches;
     }
 
-    void count() {
-        launches = launch_rows<false>();
+    void count(int* cnt) {
+        a.cnt = cnt;
+        launches = launch_waves<false>();
         plan_slots();
         run_slots<false>();
     }
 
     void fill(const int* prp, int* pcol, double* pval) {
-        a.prp = prp, a.pcol = pcol, a.pval = pval;
-        launch_rows<true>();
+        a.cnt = nullptr, a.prp = prp, a.pcol = pcol, a.pval = pval;
+        launch_waves<true>();
         run_slots<true>();
-        int e = 0;
-        HIP_CHECK(hipMemcpyAsync(&e, err.p, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
+        const int e = read_scalar(s, err.p);
         AMG_ASSERT(e == 0);
     }
 };
 
-}  // namespace
+// ---- PMIS level: the stages of pmis_level ---------------------------------------------------
+void classical_strength(LevelCtx& L, DevS& S) {
+    build_rows(L, S, strength_classical_kernel<false>, strength_classical_kernel<true>, L.Av, L.opt.strong_threshold);
+}
 
-// One level of the setup on the device: P and the integer split (C/F marker for RS-family
-// coarsening, aggregate id for SA), on any number of ranks.  Each rank works on its rows
-// with global column ids; the states of other ranks' points arrive through halo forwards
-// (pack on the device, the setup exchange on the host) -- exactly the synchronous rounds of
-// host_setup.cpp pmis_split / interp_classical / interp_ext_i / mis2_aggregate / sa_prolongator, so the
-// hierarchy is bit-identical to the host path's at every rank count.  Returns false for
-// Ruge-Stueben (the serial first pass stays on the host).
-bool level_setup_device(Context& ctx, const HostComm& comm, const HostCSR& A, const amg_options& opt,
-                        int level, HostCSR& P, std::vector<int32_t>& split, SetupImages* imgs, int64_t* ext_stats) {
-    if (ext_stats) ext_stats[0] = ext_stats[1] = 0;
-    // Ruge-Stueben (serial first pass): the host path
-    if (opt.coarsen == AMG_COARSEN_RS) return false;
-    const bool ext = opt.coarsen == AMG_COARSEN_PMIS && opt.interp == AMG_INTERP_EXT_I;
-    hipStream_t s = ctx.stream;
-    const int n = (int)A.nrows();
-    if (comm.nranks == 1 && n == 0) return false;
-    PhaseTimer tm(comm);
-    // A on the device: the setup's image (one rank: uploaded once, or left there by the
-    // previous level's Galerkin product), else uploaded for this level
-    DevLevel D;
-    DevCsr* DA = imgs ? &imgs->get(A) : nullptr;
-    if (DA) {
-        AMG_CHECK(n < INT_MAX && A.n_global_cols < INT_MAX, "device setup: level exceeds int32 indexing");
-        DA->ensure_rp32(s);
-        DA->ensure_col32(s);
-    } else {
-        upload_level(comm, A, D);
-    }
-    const int lo = (int)A.row_starts[comm.rank];
-    DevBuf<char> tmp;
-    DevS S;
-    const DCsr Av = DA ? DCsr{DA->rp32.p, DA->col32.p, DA->val.p, n, lo} : D.view();
-    if (opt.coarsen == AMG_COARSEN_PMIS) {
-        const double theta = opt.strong_threshold;
-        build_strength(
-            s, n, lo, S, tmp,
-            [&](int* cnt) {
-                if (n)
-                    hipLaunchKernelGGL(strength_classical_kernel<false>, dim3(grid1(n)), dim3(kT), 0, s, Av, theta,
-                                       cnt, nullptr, nullptr, nullptr);
-            },
-            [&](const int* srp, int* scol, double* sval) {
-                if (n)
-                    hipLaunchKernelGGL(strength_classical_kernel<true>, dim3(grid1(n)), dim3(kT), 0, s, Av, theta,
-                                       nullptr, srp, scol, sval);
-            });
-        tm.lap("  device strength");
-        const DCsr Sv = S.view();
-        // |S^T_i| and the S^T adjacency of the local-local part
-        DevBuf<int> tcnt, trp, tcol, cursor;
-        tcnt.alloc((size_t)n + 1);
-        HIP_CHECK(hipMemsetAsync(tcnt.p, 0, sizeof(int) * tcnt.n, s));
-        if (n) hipLaunchKernelGGL(col_count_kernel, dim3(grid1(n)), dim3(kT), 0, s, Sv, tcnt.p);
-        trp.alloc((size_t)n + 1);
-        const int64_t tnnz = exclusive_scan(s, tcnt.p, trp.p, n, tmp);
-        tcol.alloc((size_t)std::max<int64_t>(tnnz, 1));
-        cursor.alloc((size_t)n + 1);
-        HIP_CHECK(hipMemcpyAsync(cursor.p, trp.p, sizeof(int) * (n + 1), hipMemcpyDeviceToDevice, s));
-        if (n) hipLaunchKernelGGL(transpose_fill_kernel, dim3(grid1(n)), dim3(kT), 0, s, Sv, cursor.p, tcol.p);
-        // several ranks: off-rank dependents (pairs (i, j), j on another rank depends on local
-        // i) and the halo of the neighbourhoods S_i u S^T_i, as pmis_split builds them
-        HaloPlan hplan;
-        DevHalo H;
-        DevBuf<int> erp, ecol;
-        if (comm.nranks > 1) {
-            DevBuf<int> ocnt, orp, opc, opj;
-            ocnt.alloc((size_t)n + 1);
-            HIP_CHECK(hipMemsetAsync(ocnt.p, 0, sizeof(int) * ocnt.n, s));
-            if (n)
-                hipLaunchKernelGGL(offrank_kernel<false>, dim3(grid1(n)), dim3(kT), 0, s, Sv, ocnt.p, nullptr,
-                                   nullptr, nullptr);
-            orp.alloc((size_t)n + 1);
-            const int64_t no = exclusive_scan(s, ocnt.p, orp.p, n, tmp);
-            opc.alloc((size_t)std::max<int64_t>(no, 1));
-            opj.alloc((size_t)std::max<int64_t>(no, 1));
-            if (n)
-                hipLaunchKernelGGL(offrank_kernel<true>, dim3(grid1(n)), dim3(kT), 0, s, Sv, nullptr, orp.p, opc.p,
-                                   opj.p);
-            const std::vector<int32_t> pc = download_ints(s, opc.p, no), pj = download_ints(s, opj.p, no);
-            std::vector<std::vector<int64_t>> sendp(comm.nranks);
-            std::vector<int64_t> need;
-            for (int64_t t = 0; t < no; ++t) {
-                const int o = owner_of(A.col_starts, pc[t]);
-                sendp[o].push_back(pc[t]);
-                sendp[o].push_back(pj[t]);
-                need.push_back(pc[t]);
-            }
-            const auto gotp = comm.exchange(sendp);
-            std::vector<int> ec((size_t)n + 1, 0);
-            for (int r = 0; r < comm.nranks; ++r)
-                for (size_t t = 0; t < gotp[r].size(); t += 2) ++ec[gotp[r][t] - lo + 1];
-            for (int i = 0; i < n; ++i) ec[i + 1] += ec[i];
-            std::vector<int> el((size_t)std::max(ec[n], 1)), pos(ec.begin(), ec.end() - 1);
-            for (int r = 0; r < comm.nranks; ++r)
-                for (size_t t = 0; t < gotp[r].size(); t += 2) {
-                    el[pos[gotp[r][t] - lo]++] = (int)gotp[r][t + 1];
-                    need.push_back(gotp[r][t + 1]);
-                }
-            erp.upload(ec.data(), ec.size());
-            ecol.upload(el.data(), el.size());
-            hplan = build_halo_plan(comm, A.col_starts, std::move(need));
-        }
-        H.build(hplan);
-        const Dist Dn = H.dist(lo, n);
-        DevBuf<unsigned long long> key, hkey, nu;
-        DevBuf<int> cf, hcf;
-        DevBuf<unsigned char> newc;
-        key.alloc((size_t)std::max(n, 1));
-        cf.alloc((size_t)std::max(n, 1));
-        newc.alloc((size_t)std::max(n, 1));
-        nu.alloc(1);
-        hkey.alloc(1);
-        hcf.alloc(1);
-        if (n)
-            hipLaunchKernelGGL(pmis_init_kernel, dim3(grid1(n)), dim3(kT), 0, s, n, lo, tcnt.p,
-                               comm.nranks > 1 ? erp.p : nullptr, (unsigned long long)(opt.seed + (uint64_t)level),
-                               key.p, cf.p);
-        HIP_CHECK(hipGetLastError());
-        const bool dist = comm.nranks > 1;
-        if (dist) H.forward(s, comm, key.p, hkey);
-        for (int round = 0;; ++round) {
-            AMG_CHECK(round <= A.n_global_rows, "PMIS did not terminate");
-            if (dist) H.forward(s, comm, cf.p, hcf);
-            if (n) {
-                hipLaunchKernelGGL(pmis_select_kernel, dim3(grid1(n)), dim3(kT), 0, s, Sv, Dn, trp.p, tcol.p,
-                                   dist ? erp.p : nullptr, dist ? ecol.p : nullptr, key.p, hkey.p, cf.p, hcf.p,
-                                   newc.p);
-                hipLaunchKernelGGL(pmis_apply_kernel, dim3(grid1(n)), dim3(kT), 0, s, n, newc.p, cf.p);
-            }
-            if (dist) H.forward(s, comm, cf.p, hcf);
-            HIP_CHECK(hipMemsetAsync(nu.p, 0, sizeof(unsigned long long), s));
-            if (n) hipLaunchKernelGGL(pmis_fpass_kernel, dim3(grid1(n)), dim3(kT), 0, s, Sv, Dn, cf.p, hcf.p, nu.p);
-            HIP_CHECK(hipGetLastError());
-            unsigned long long left = 0;
-            HIP_CHECK(hipMemcpyAsync(&left, nu.p, sizeof(left), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            const int64_t all = dist ? comm.allreduce_sum((int64_t)left) : (int64_t)left;
-            if (all == 0) break;
-        }
-        tm.lap("  device PMIS");
-        // coarse numbering: C points in row order, ranks in order
-        split = download_ints(s, cf.p, n);
-        int64_t ncl = 0;
-        for (int32_t v : split) ncl += v == ST_C;
-        std::vector<int64_t> cstarts(comm.nranks + 1, 0);
-        {
-            const std::vector<int64_t> counts = comm.allgather(ncl);
-            for (int r = 0; r < comm.nranks; ++r) cstarts[r + 1] = cstarts[r] + counts[r];
-        }
-        AMG_CHECK(cstarts[comm.nranks] < INT_MAX, "device setup: coarse level exceeds int32 indexing");
-        std::vector<int> hcmap((size_t)std::max(n, 1), -1);
-        for (int i = 0, c = (int)cstarts[comm.rank]; i < n; ++i)
-            if (split[i] == ST_C) hcmap[i] = c++;
-        DevBuf<int> cmap;
-        cmap.upload(hcmap.data(), hcmap.size());
-        // A's halo: states and coarse ids of the off-rank columns, and their ghost rows
-        HaloPlan aplan;
-        GhostRows G;
-        if (dist) {
-            aplan = halo_plan_for_cols(comm, A);
-            G = fetch_rows(comm, aplan, A);
-        }
-        DevHalo AH;
-        AH.build(aplan);
-        DevBuf<int> acf, acmap, grp, gcol;
-        DevBuf<double> gval;
-        acf.alloc(1);
-        acmap.alloc(1);
-        if (dist) {
-            std::vector<int32_t> hcfa(aplan.n_halo());
-            std::vector<int64_t> cm64(hcmap.begin(), hcmap.begin() + n), hcm64(aplan.n_halo());
-            aplan.forward(comm, split.data(), hcfa.data());
-            aplan.forward(comm, cm64.data(), hcm64.data());
-            std::vector<int> hcma(hcm64.begin(), hcm64.end());
-            acf.upload(hcfa.data(), hcfa.size());
-            acmap.upload(hcma.data(), hcma.size());
-            AMG_CHECK(G.rp.back() < INT_MAX, "device setup: ghost rows exceed int32 indexing");
-            std::vector<int> gr(G.rp.begin(), G.rp.end()), gc(G.col.begin(), G.col.end());
-            grp.upload(gr.data(), gr.size());
-            gcol.upload(gc.data(), std::max<size_t>(gc.size(), 1));
-            gval.upload(G.val.data(), std::max<size_t>(G.val.size(), 1));
-        } else {
-            grp.alloc(1);
-            gcol.alloc(1);
-            gval.alloc(1);
-        }
-        const ARows Ar{Av, AH.dist(lo, n), grp.p, gcol.p, gval.p};
-        tm.lap("  device coarse ids + ghost rows");
-        // P: count, scan, fill
-        DevBuf<int> pcnt, prp, pcol;
-        DevBuf<double> pval;
-        pcnt.alloc((size_t)n + 1);
-        HIP_CHECK(hipMemsetAsync(pcnt.p, 0, sizeof(int) * pcnt.n, s));
-        // extended+i: the state halo two deep (cf and coarse ids), then count / scan / fill too
-        ExtInterp X;
-        if (ext) X.init(s, comm, A, aplan, G, Ar, Sv, cf.p, cmap.p, (int)cstarts[comm.nranks], opt, pcnt.p);
-        // long rows (the Galerkin levels): a wave per row (interp_wave_kernel); AMG_INTERP_WAVE_NPR
-        // sets the average row length from which it is taken (default 12; 0: always)
-        const char* wenv = std::getenv("AMG_INTERP_WAVE_NPR");
-        const int wave_npr = wenv && *wenv ? std::atoi(wenv) : 12;
-        const bool wave = n > 0 && A.nnz() >= (int64_t)wave_npr * n;
-        const dim3 wgrid((unsigned)((n + kIwWaves - 1) / kIwWaves)), wblk(64 * kIwWaves);
-        if (n && ext)
-            X.count();
-        else if (n && wave)
-            hipLaunchKernelGGL(interp_wave_kernel<false>, wgrid, wblk, 0, s, Ar, Sv, cf.p, acf.p, cmap.p, acmap.p,
-                               pcnt.p, nullptr, nullptr, nullptr);
-        else if (n)
-            hipLaunchKernelGGL(interp_kernel<false>, dim3(grid1(n)), dim3(kT), 0, s, Ar, Sv, cf.p, acf.p, cmap.p,
-                               acmap.p, pcnt.p, nullptr, nullptr, nullptr);
-        prp.alloc((size_t)n + 1);
-        const int64_t pnnz = exclusive_scan(s, pcnt.p, prp.p, n, tmp);
-        pcol.alloc((size_t)std::max<int64_t>(pnnz, 1));
-        pval.alloc((size_t)std::max<int64_t>(pnnz, 1));
-        if (n && ext)
-            X.fill(prp.p, pcol.p, pval.p);
-        else if (n && wave)
-            hipLaunchKernelGGL(interp_wave_kernel<true>, wgrid, wblk, 0, s, Ar, Sv, cf.p, acf.p, cmap.p, acmap.p,
-                               nullptr, prp.p, pcol.p, pval.p);
-        else if (n)
-            hipLaunchKernelGGL(interp_kernel<true>, dim3(grid1(n)), dim3(kT), 0, s, Ar, Sv, cf.p, acf.p, cmap.p,
-                               acmap.p, nullptr, prp.p, pcol.p, pval.p);
-        HIP_CHECK(hipGetLastError());
-        std::vector<int> hrp = download_ints(s, prp.p, (int64_t)n + 1), hcol = download_ints(s, pcol.p, pnnz);
-        P = HostCSR();
-        P.n_global_rows = A.n_global_rows;
-        P.n_global_cols = cstarts[comm.nranks];
-        P.row_starts = A.row_starts;
-        P.col_starts = cstarts;
-        P.rp.assign(hrp.begin(), hrp.end());
-        P.col.assign(hcol.begin(), hcol.end());
-        P.val.resize((size_t)pnnz);
-        copy_to_host(P.val.data(), pval.p, sizeof(double) * pnnz, s);
-        if (imgs) {  // P where it was computed, for the transpose and the Galerkin product
-            std::unique_ptr<DevCsr> d(new DevCsr());
-            d->rp32 = std::move(prp);
-            d->col32 = std::move(pcol);
-            d->val = std::move(pval);
-            imgs->put(P, std::move(d));
-        }
-        if (ext && ext_stats) ext_stats[0] = (int64_t)X.slots.size(), ext_stats[1] = X.launches;
-        tm.lap(ext ? "  device interpolation (" + std::to_string(X.slots.size()) + " scratch rows)"
-                   : std::string("  device interpolation"));
-        return true;
-    }
-    // smoothed aggregation (host_setup.cpp strength_symmetric, mis2_aggregate, sa_prolongator)
-    AMG_CHECK(opt.coarsen == AMG_COARSEN_SA, "unknown coarsening");
-    const bool dist = comm.nranks > 1;
-    const double theta = sa_theta(opt.strong_threshold, level);
-    // A's halo: a_jj of other ranks' columns, then the MIS(2) tuples and aggregate ids of the
-    // strong neighbours (S is a subset of A's pattern)
-    HaloPlan aplan;
-    if (dist) aplan = halo_plan_for_cols(comm, A);
-    DevHalo AH;
-    AH.build(aplan);
-    const Dist Da = AH.dist(lo, n);
-    DevBuf<double> d, hd;
-    d.alloc((size_t)std::max(n, 1));
-    hd.alloc(1);
-    if (n) hipLaunchKernelGGL(diagonal_kernel, dim3(grid1(n)), dim3(kT), 0, s, Av, d.p);
-    if (dist) AH.forward(s, comm, d.p, hd);
-    build_strength(
-        s, n, lo, S, tmp,
-        [&](int* cnt) {
-            if (n)
-                hipLaunchKernelGGL(strength_symmetric_kernel<false>, dim3(grid1(n)), dim3(kT), 0, s, Av, Da, d.p,
-                                   hd.p, theta, cnt, nullptr, nullptr, nullptr);
-        },
-        [&](const int* srp, int* scol, double* sval) {
-            if (n)
-                hipLaunchKernelGGL(strength_symmetric_kernel<true>, dim3(grid1(n)), dim3(kT), 0, s, Av, Da, d.p,
-                                   hd.p, theta, nullptr, srp, scol, sval);
+// several ranks: off-rank dependents (pairs (i, j), j on another rank depends on local i) as the
+// rows erp / ecol, and the halo plan of the neighbourhoods S_i u S^T_i, as pmis_split builds them
+HaloPlan offrank_dependents(LevelCtx& L, const DCsr& Sv, DevBuf<int>& erp, DevBuf<int>& ecol) {
+    const HostComm& comm = L.comm;
+    const int n = L.n, lo = L.lo;
+    DevBuf<int> orp, opc, opj;
+    const int64_t no = count_scan_fill(
+        L.s, n, orp, L.tmp,
+        [&](int* cnt) { launch_rows(L.s, n, offrank_kernel<false>, Sv, cnt, nullptr, nullptr, nullptr); },
+        [&](const int* rp, int64_t total) {
+            opc.alloc((size_t)std::max<int64_t>(total, 1));
+            opj.alloc((size_t)std::max<int64_t>(total, 1));
+            launch_rows(L.s, n, offrank_kernel<true>, Sv, nullptr, rp, opc.p, opj.p);
         });
-    tm.lap("  device strength");
-    const DCsr Sv = S.view();
-    std::vector<unsigned> hs((size_t)std::max(n, 1));
-    for (int i = 0; i < n; ++i) hs[i] = hash32(lo + i, opt.seed + (uint64_t)level);
+    const std::vector<int32_t> pc = download_ints(L.s, opc.p, no), pj = download_ints(L.s, opj.p, no);
+    std::vector<std::vector<int64_t>> sendp(comm.nranks);
+    std::vector<int64_t> need;
+    for (int64_t t = 0; t < no; ++t) {
+        const int o = owner_of(L.A.col_starts, pc[t]);
+        sendp[o].push_back(pc[t]);
+        sendp[o].push_back(pj[t]);
+        need.push_back(pc[t]);
+    }
+    const auto gotp = comm.exchange(sendp);
+    std::vector<int> ec((size_t)n + 1, 0);
+    for (int r = 0; r < comm.nranks; ++r)
+        for (size_t t = 0; t < gotp[r].size(); t += 2) ++ec[gotp[r][t] - lo + 1];
+    for (int i = 0; i < n; ++i) ec[i + 1] += ec[i];
+    std::vector<int> el((size_t)std::max(ec[n], 1)), pos(ec.begin(), ec.end() - 1);
+    for (int r = 0; r < comm.nranks; ++r)
+        for (size_t t = 0; t < gotp[r].size(); t += 2) {
+            el[pos[gotp[r][t] - lo]++] = (int)gotp[r][t + 1];
+            need.push_back(gotp[r][t + 1]);
+        }
+    erp.upload(ec.data(), ec.size());
+    ecol.upload(el.data(), el.size());
+    return build_halo_plan(comm, L.A.col_starts, std::move(need));
+}
+
+// the C/F states cf.  The S^T adjacency, the keys, the off-rank lists and their halo are the
+// stage's own: freed on return, before interpolation (the level's peak)
+void pmis_split(LevelCtx& L, const DCsr& Sv, DevBuf<int>& cf) {
+    hipStream_t s = L.s;
+    const HostComm& comm = L.comm;
+    const int n = L.n, lo = L.lo;
+    const bool dist = L.dist;
+    // |S^T_i| and the S^T adjacency of the local-local part
+    DevBuf<int> tcnt, trp, tcol, cursor;
+    tcnt.alloc((size_t)n + 1);
+    HIP_CHECK(hipMemsetAsync(tcnt.p, 0, sizeof(int) * tcnt.n, s));
+    launch_rows(s, n, col_count_kernel, Sv, tcnt.p);
+    trp.alloc((size_t)n + 1);
+    const int64_t tnnz = exclusive_scan(s, tcnt.p, trp.p, n, L.tmp);
+    tcol.alloc((size_t)std::max<int64_t>(tnnz, 1));
+    cursor.alloc((size_t)n + 1);
+    HIP_CHECK(hipMemcpyAsync(cursor.p, trp.p, sizeof(int) * (n + 1), hipMemcpyDeviceToDevice, s));
+    launch_rows(s, n, transpose_fill_kernel, Sv, cursor.p, tcol.p);
+    DevBuf<int> erp, ecol;
+    DevHalo H;
+    H.build(dist ? offrank_dependents(L, Sv, erp, ecol) : HaloPlan());
+    const Dist Dn = H.dist(lo, n);
+    DevBuf<unsigned long long> key, hkey, nu;
+    DevBuf<int> hcf;
+    DevBuf<unsigned char> newc;
+    key.alloc((size_t)std::max(n, 1));
+    cf.alloc((size_t)std::max(n, 1));
+    newc.alloc((size_t)std::max(n, 1));
+    nu.alloc(1);
+    hkey.alloc(1);
+    hcf.alloc(1);
+    launch_rows(s, n, pmis_init_kernel, n, lo, tcnt.p, dist ? erp.p : nullptr, (unsigned long long)L.seed(), key.p,
+                cf.p);
+    if (dist) H.forward(s, comm, key.p, hkey);
+    for (int round = 0;; ++round) {
+        AMG_CHECK(round <= L.A.n_global_rows, "PMIS did not terminate");
+        if (dist) H.forward(s, comm, cf.p, hcf);
+        launch_rows(s, n, pmis_select_kernel, Sv, Dn, trp.p, tcol.p, dist ? erp.p : nullptr,
+                    dist ? ecol.p : nullptr, key.p, hkey.p, cf.p, hcf.p, newc.p);
+        launch_rows(s, n, pmis_apply_kernel, n, newc.p, cf.p);
+        if (dist) H.forward(s, comm, cf.p, hcf);
+        HIP_CHECK(hipMemsetAsync(nu.p, 0, sizeof(unsigned long long), s));
+        launch_rows(s, n, pmis_fpass_kernel, Sv, Dn, cf.p, hcf.p, nu.p);
+        const int64_t left = (int64_t)read_scalar(s, nu.p);
+        if ((dist ? comm.allreduce_sum(left) : left) == 0) break;
+    }
+}
+
+// coarse numbering: C points in row order, ranks in order
+struct CoarseIds : Pinned {
+    std::vector<int64_t> cstarts;  // the coarse partition
+    std::vector<int> host;         // coarse id of a local C row, else -1
+    DevBuf<int> cmap;              // the same on the device
+};
+
+void coarse_numbering(LevelCtx& L, const DevBuf<int>& cf, std::vector<int32_t>& split, CoarseIds& C) {
+    const HostComm& comm = L.comm;
+    const int n = L.n;
+    split = download_ints(L.s, cf.p, n);
+    int64_t ncl = 0;
+    for (int32_t v : split) ncl += v == ST_C;
+    C.cstarts.assign(comm.nranks + 1, 0);
+    {
+        const std::vector<int64_t> counts = comm.allgather(ncl);
+        for (int r = 0; r < comm.nranks; ++r) C.cstarts[r + 1] = C.cstarts[r] + counts[r];
+    }
+    AMG_CHECK(C.cstarts[comm.nranks] < INT_MAX, "device setup: coarse level exceeds int32 indexing");
+    C.host.assign((size_t)std::max(n, 1), -1);
+    for (int i = 0, c = (int)C.cstarts[comm.rank]; i < n; ++i)
+        if (split[i] == ST_C) C.host[i] = c++;
+    C.cmap.upload(C.host.data(), C.host.size());
+}
+
+// A's halo: states and coarse ids of the off-rank columns, and their ghost rows
+struct AHalo : Pinned {
+    DevHalo AH;
+    GhostRows G;
+    DevBuf<int> acf, acmap, grp, gcol;
+    DevBuf<double> gval;
+    ARows rows(const LevelCtx& L) const { return ARows{L.Av, AH.dist(L.lo, L.n), grp.p, gcol.p, gval.p}; }
+};
+
+void a_halo_and_ghost_rows(LevelCtx& L, const std::vector<int32_t>& split, const CoarseIds& C, AHalo& H) {
+    const HostComm& comm = L.comm;
+    H.AH.build(L.dist ? halo_plan_for_cols(comm, L.A) : HaloPlan());
+    const HaloPlan& aplan = H.AH.plan;
+    H.acf.alloc(1);
+    H.acmap.alloc(1);
+    if (!L.dist) {
+        H.grp.alloc(1);
+        H.gcol.alloc(1);
+        H.gval.alloc(1);
+        return;
+    }
+    GhostRows& G = H.G;
+    G = fetch_rows(comm, aplan, L.A);
+    std::vector<int32_t> hcfa(aplan.n_halo());
+    std::vector<int64_t> cm64(C.host.begin(), C.host.begin() + L.n), hcm64(aplan.n_halo());
+    aplan.forward(comm, split.data(), hcfa.data());
+    aplan.forward(comm, cm64.data(), hcm64.data());
+    std::vector<int> hcma(hcm64.begin(), hcm64.end());
+    H.acf.upload(hcfa.data(), hcfa.size());
+    H.acmap.upload(hcma.data(), hcma.size());
+    AMG_CHECK(G.rp.back() < INT_MAX, "device setup: ghost rows exceed int32 indexing");
+    std::vector<int> gr(G.rp.begin(), G.rp.end()), gc(G.col.begin(), G.col.end());
+    H.grp.upload(gr.data(), gr.size());
+    H.gcol.upload(gc.data(), std::max<size_t>(gc.size(), 1));
+    H.gval.upload(G.val.data(), std::max<size_t>(G.val.size(), 1));
+}
+
+// P's rows: classical interpolation a thread or a wave per row, or extended+i (X: the state halo
+// two deep, then count / scan / fill too)
+void interpolate(LevelCtx& L, const DCsr& Sv, const DevBuf<int>& cf, const CoarseIds& C, const AHalo& H, ExtInterp& X,
+                 DevRows<int>& p) {
+    hipStream_t s = L.s;
+    const int n = L.n;
+    const ARows Ar = H.rows(L);
+    const bool ext = L.opt.interp == AMG_INTERP_EXT_I;
+    if (ext)
+        X.init(s, L.comm, L.A, H.AH.plan, H.G, Ar, Sv, cf.p, C.cmap.p, (int)C.cstarts[L.comm.nranks], L.opt);
+    // long rows (the Galerkin levels): a wave per row (interp_wave_kernel); AMG_INTERP_WAVE_NPR
+    // sets the average row length from which it is taken (default 12; 0: always)
+    const char* wenv = std::getenv("AMG_INTERP_WAVE_NPR");
+    const int wave_npr = wenv && *wenv ? std::atoi(wenv) : 12;
+    const bool wave = n > 0 && L.A.nnz() >= (int64_t)wave_npr * n;
+    const dim3 wgrid((unsigned)((n + kIwWaves - 1) / kIwWaves)), wblk(64 * kIwWaves);
+    build_rows_with(
+        L, p,
+        [&](int* cnt) {
+            if (n && ext)
+                X.count(cnt);
+            else if (wave)
+                hipLaunchKernelGGL(interp_wave_kernel<false>, wgrid, wblk, 0, s, Ar, Sv, cf.p, H.acf.p, C.cmap.p,
+                                   H.acmap.p, cnt, nullptr, nullptr, nullptr);
+            else
+                launch_rows(s, n, interp_kernel<false>, Ar, Sv, cf.p, H.acf.p, C.cmap.p, H.acmap.p, cnt, nullptr,
+                            nullptr, nullptr);
+        },
+        [&](const int* prp, int* pcol, double* pval) {
+            if (n && ext)
+                X.fill(prp, pcol, pval);
+            else if (wave)
+                hipLaunchKernelGGL(interp_wave_kernel<true>, wgrid, wblk, 0, s, Ar, Sv, cf.p, H.acf.p, C.cmap.p,
+                                   H.acmap.p, nullptr, prp, pcol, pval);
+            else
+                launch_rows(s, n, interp_kernel<true>, Ar, Sv, cf.p, H.acf.p, C.cmap.p, H.acmap.p, nullptr, prp, pcol,
+                            pval);
+        });
+}
+
+template <class I, class V>
+void download_index(hipStream_t s, const I* p, int64_t n, V& out) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "int64 columns");
+    if constexpr (std::is_same<I, int>::value) {
+        const std::vector<int32_t> h = download_ints(s, p, n);
+        out.assign(h.begin(), h.end());
+    } else {
+        out.resize((size_t)n);
+        copy_to_host(out.data(), p, sizeof(long long) * n, s);
+    }
+}
+
+// P on the host, columns partitioned by cstarts; with imgs, the device arrays become P's image
+// (where it was computed, for the transpose and the Galerkin product) -- int32 or int64 indices
+template <class I>
+void take_P(LevelCtx& L, DevRows<I>& p, const std::vector<int64_t>& cstarts, HostCSR& P, SetupImages* imgs) {
+    P = HostCSR();
+    P.n_global_rows = L.A.n_global_rows;
+    P.n_global_cols = cstarts[L.comm.nranks];
+    P.row_starts = L.A.row_starts;
+    P.col_starts = cstarts;
+    download_index(L.s, p.rp.p, (int64_t)L.n + 1, P.rp);
+    download_index(L.s, p.col.p, p.nnz, P.col);
+    P.val.resize((size_t)p.nnz);
+    copy_to_host(P.val.data(), p.val.p, sizeof(double) * p.nnz, L.s);
+    if (!imgs) return;
+    std::unique_ptr<DevCsr> d(new DevCsr());
+    if constexpr (std::is_same<I, int>::value) {
+        d->rp32 = std::move(p.rp);
+        d->col32 = std::move(p.col);
+    } else {
+        d->rp64 = std::move(p.rp);
+        d->col64 = std::move(p.col);
+    }
+    d->val = std::move(p.val);
+    imgs->put(P, std::move(d));
+}
+
+// PMIS coarsening with classical or extended+i interpolation (host_setup.cpp pmis_split /
+// interp_classical / interp_ext_i)
+bool pmis_level(LevelCtx& L, HostCSR& P, std::vector<int32_t>& split, SetupImages& im, int64_t* ext_stats) {
+    DevS S;
+    classical_strength(L, S);
+    L.tm.lap("  device strength");
+    DevBuf<int> cf;
+    pmis_split(L, view(L, S), cf);
+    L.tm.lap("  device PMIS");
+    CoarseIds C;
+    coarse_numbering(L, cf, split, C);
+    AHalo H;
+    a_halo_and_ghost_rows(L, split, C, H);
+    L.tm.lap("  device coarse ids + ghost rows");
+    const bool ext = L.opt.interp == AMG_INTERP_EXT_I;
+    ExtInterp X;
+    DevRows<int> p;
+    interpolate(L, view(L, S), cf, C, H, X, p);
+    take_P(L, p, C.cstarts, P, &im);
+    if (ext && ext_stats) ext_stats[0] = (int64_t)X.slots.size(), ext_stats[1] = X.launches;
+    L.tm.lap(ext ? "  device interpolation (" + std::to_string(X.slots.size()) + " scratch rows)"
+                 : std::string("  device interpolation"));
+    return true;
+}
+
+// ---- SA level: the stages of sa_level ---------------------------------------------------------
+// A's halo: a_jj of other ranks' columns, then the MIS(2) tuples, aggregate ids and weights of the
+// strong neighbours (S is a subset of A's pattern); read by every stage
+struct SaHalo : Pinned {
+    double theta = 0.0;
+    DevHalo AH;
+    DevBuf<double> d, hd;  // a_ii, and of the halo columns
+};
+
+void symmetric_strength(LevelCtx& L, SaHalo& H, DevS& S) {
+    hipStream_t s = L.s;
+    const int n = L.n;
+    H.theta = sa_theta(L.opt.strong_threshold, L.level);
+    H.AH.build(L.dist ? halo_plan_for_cols(L.comm, L.A) : HaloPlan());
+    const Dist Da = H.AH.dist(L.lo, n);
+    H.d.alloc((size_t)std::max(n, 1));
+    H.hd.alloc(1);
+    launch_rows(s, n, diagonal_kernel, L.Av, H.d.p);
+    if (L.dist) H.AH.forward(s, L.comm, H.d.p, H.hd);
+    build_rows(L, S, strength_symmetric_kernel<false>, strength_symmetric_kernel<true>, L.Av, Da, H.d.p, H.hd.p,
+               H.theta);
+}
+
+// the MIS(2) rounds: st[i] == M_IN marks the roots.  The hops swap the raw pointers of h0 / h1
+// and l0 / l1, which are all this function's
+void mis2_rounds(LevelCtx& L, const SaHalo& H, const DCsr& Sv, DevBuf<int>& st) {
+    hipStream_t s = L.s;
+    const HostComm& comm = L.comm;
+    const int n = L.n, lo = L.lo;
+    const bool dist = L.dist;
+    const Dist Da = H.AH.dist(lo, n);
+    const size_t nn = (size_t)std::max(n, 1);
+    std::vector<unsigned> hs(nn);
+    for (int i = 0; i < n; ++i) hs[i] = hash32(lo + i, L.seed());
     DevBuf<unsigned> dhs;
     dhs.upload(hs.data(), hs.size());
-    DevBuf<int> st;
     DevBuf<unsigned long long> h0, l0, h1, l1, hh, hl, nu;
-    const size_t nn = (size_t)std::max(n, 1);
-    st.alloc(nn);
     h0.alloc(nn), l0.alloc(nn), h1.alloc(nn), l1.alloc(nn), nu.alloc(1), hh.alloc(1), hl.alloc(1);
     {
         std::vector<int> init(nn, M_U);
         st.upload(init.data(), init.size());
     }
     for (int round = 0;; ++round) {
-        AMG_CHECK(round <= A.n_global_rows, "MIS(2) did not terminate");
-        if (n) hipLaunchKernelGGL(mis2_tuple_kernel, dim3(grid1(n)), dim3(kT), 0, s, n, lo, st.p, dhs.p, h0.p, l0.p);
+        AMG_CHECK(round <= L.A.n_global_rows, "MIS(2) did not terminate");
+        launch_rows(s, n, mis2_tuple_kernel, n, lo, st.p, dhs.p, h0.p, l0.p);
         for (int hop = 0; hop < 2; ++hop) {
             if (dist) {
-                AH.forward(s, comm, h0.p, hh);
-                AH.forward(s, comm, l0.p, hl);
+                H.AH.forward(s, comm, h0.p, hh);
+                H.AH.forward(s, comm, l0.p, hl);
             }
-            if (n)
-                hipLaunchKernelGGL(mis2_hop_kernel, dim3(grid1(n)), dim3(kT), 0, s, Sv, Da, h0.p, l0.p, hh.p, hl.p,
-                                   h1.p, l1.p);
+            launch_rows(s, n, mis2_hop_kernel, Sv, Da, h0.p, l0.p, hh.p, hl.p, h1.p, l1.p);
             std::swap(h0.p, h1.p);
             std::swap(l0.p, l1.p);
         }
         HIP_CHECK(hipMemsetAsync(nu.p, 0, sizeof(unsigned long long), s));
-        if (n) hipLaunchKernelGGL(mis2_update_kernel, dim3(grid1(n)), dim3(kT), 0, s, n, lo, h0.p, l0.p, st.p, nu.p);
-        HIP_CHECK(hipGetLastError());
-        unsigned long long left = 0;
-        HIP_CHECK(hipMemcpyAsync(&left, nu.p, sizeof(left), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if ((dist ? comm.allreduce_sum((int64_t)left) : (int64_t)left) == 0) break;
+        launch_rows(s, n, mis2_update_kernel, n, lo, h0.p, l0.p, st.p, nu.p);
+        const int64_t left = (int64_t)read_scalar(s, nu.p);
+        if ((dist ? comm.allreduce_sum(left) : left) == 0) break;
     }
-    // roots numbered in global row order (ranks in order); aggr = a root's aggregate id, -1
-    // (r5: an exclusive scan of the root flags on the device, not a host pass over the states)
+}
+
+struct Aggregates : Pinned {
+    std::vector<int64_t> astarts;  // the partition of the aggregates (the coarse columns)
+    DevBuf<int> agg;               // aggregate of every local row (split on the host)
+};
+
+// roots numbered in global row order (ranks in order) by an exclusive scan of the root flags;
+// aggr = a root's aggregate id, -1; then the two joining passes
+void mis2_aggregate(LevelCtx& L, const SaHalo& H, const DCsr& Sv, Aggregates& ag, std::vector<int32_t>& split) {
+    hipStream_t s = L.s;
+    const HostComm& comm = L.comm;
+    const int n = L.n;
+    const bool dist = L.dist;
+    const Dist Da = H.AH.dist(L.lo, n);
+    const size_t nn = (size_t)std::max(n, 1);
+    DevBuf<int> st;
+    mis2_rounds(L, H, Sv, st);
     DevBuf<int> rflag, rpos;
     rflag.alloc(nn + 1);
     rpos.alloc(nn + 1);
     HIP_CHECK(hipMemsetAsync(rflag.p, 0, sizeof(int) * rflag.n, s));
-    if (n) hipLaunchKernelGGL(root_flag_kernel, dim3(grid1(n)), dim3(kT), 0, s, n, st.p, rflag.p);
-    const int64_t nroot = exclusive_scan(s, rflag.p, rpos.p, n, tmp);
-    std::vector<int64_t> astarts(comm.nranks + 1, 0);
+    launch_rows(s, n, root_flag_kernel, n, st.p, rflag.p);
+    const int64_t nroot = exclusive_scan(s, rflag.p, rpos.p, n, L.tmp);
+    ag.astarts.assign(comm.nranks + 1, 0);
     {
         const std::vector<int64_t> counts = comm.allgather(nroot);
-        for (int r = 0; r < comm.nranks; ++r) astarts[r + 1] = astarts[r] + counts[r];
+        for (int r = 0; r < comm.nranks; ++r) ag.astarts[r + 1] = ag.astarts[r] + counts[r];
     }
-    const int64_t na = astarts[comm.nranks];
-    AMG_CHECK(na < INT_MAX, "device setup: coarse level exceeds int32 indexing");
-    DevBuf<int> aggr, haggr_d, a1, ha1, agg;
+    AMG_CHECK(ag.astarts[comm.nranks] < INT_MAX, "device setup: coarse level exceeds int32 indexing");
+    DevBuf<int> aggr, haggr, a1, ha1;
+    DevBuf<unsigned long long> nu;
     aggr.alloc(nn);
-    if (n)
-        hipLaunchKernelGGL(root_id_kernel, dim3(grid1(n)), dim3(kT), 0, s, n, st.p, rpos.p,
-                           (int)astarts[comm.rank], aggr.p);
-    haggr_d.alloc(1);
+    launch_rows(s, n, root_id_kernel, n, st.p, rpos.p, (int)ag.astarts[comm.rank], aggr.p);
+    haggr.alloc(1);
     ha1.alloc(1);
     a1.alloc(nn);
-    agg.alloc(nn);
-    if (dist) AH.forward(s, comm, aggr.p, haggr_d);
-    if (n) hipLaunchKernelGGL(mis2_pass1_kernel, dim3(grid1(n)), dim3(kT), 0, s, Sv, Da, aggr.p, haggr_d.p, a1.p);
-    if (dist) AH.forward(s, comm, a1.p, ha1);
+    ag.agg.alloc(nn);
+    nu.alloc(1);
+    if (dist) H.AH.forward(s, comm, aggr.p, haggr);
+    launch_rows(s, n, mis2_pass1_kernel, Sv, Da, aggr.p, haggr.p, a1.p);
+    if (dist) H.AH.forward(s, comm, a1.p, ha1);
     HIP_CHECK(hipMemsetAsync(nu.p, 0, sizeof(unsigned long long), s));
-    if (n)
-        hipLaunchKernelGGL(mis2_pass2_kernel, dim3(grid1(n)), dim3(kT), 0, s, Sv, Da, a1.p, ha1.p, agg.p, nu.p);
-    HIP_CHECK(hipGetLastError());
-    unsigned long long orphans = 0;
-    HIP_CHECK(hipMemcpyAsync(&orphans, nu.p, sizeof(orphans), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (orphans) throw Error(AMG_ERR_INTERNAL, "MIS(2): unaggregated node");
-    split = download_ints(s, agg.p, n);
-    tm.lap("  device aggregation");
-    // aggregate sizes (owners count their members, members elsewhere report in), T = 1 /
-    // sqrt(|aggregate|)
+    launch_rows(s, n, mis2_pass2_kernel, Sv, Da, a1.p, ha1.p, ag.agg.p, nu.p);
+    if (read_scalar(s, nu.p)) throw Error(AMG_ERR_INTERNAL, "MIS(2): unaggregated node");
+    split = download_ints(s, ag.agg.p, n);
+}
+
+// aggregate sizes (owners count their members, members elsewhere report in), T = 1 /
+// sqrt(|aggregate|): dt, and hdt of the halo columns (A_F T)
+struct Tentative : Pinned {
+    DevBuf<double> dt, hdt;
+};
+
+void tentative_weights(LevelCtx& L, const SaHalo& H, const std::vector<int32_t>& split,
+                       const std::vector<int64_t>& astarts, Tentative& T) {
+    const HostComm& comm = L.comm;
+    const int n = L.n;
+    const bool dist = L.dist;
     const int64_t alo = astarts[comm.rank], ahi = astarts[comm.rank + 1];
     std::vector<int64_t> size((size_t)(ahi - alo), 0);
     std::vector<std::vector<int64_t>> sendc(comm.nranks);
@@ -2005,105 +2001,127 @@ bool level_setup_device(Context& ctx, const HostComm& comm, const HostCSR& A, co
         const int64_t sz = (a >= alo && a < ahi) ? size[a - alo] : hsize[splan.find(a)];
         tv[i] = 1.0 / std::sqrt((double)sz);
     }
-    DevBuf<double> dt, hdt;
-    dt.upload(tv.data(), tv.size());
-    hdt.alloc(1);
-    if (dist) AH.forward(s, comm, dt.p, hdt);  // t of the halo columns (A_F T)
-    tm.lap("  device tentative prolongator");
-    // the filtered operator A_F (r6): the diagonal + the strong couplings, weak ones lumped
-    DevS F;
-    build_strength(
-        s, n, lo, F, tmp,
-        [&](int* cnt) {
-            if (n)
-                hipLaunchKernelGGL(sa_filter_kernel<false>, dim3(grid1(n)), dim3(kT), 0, s, Av, Da, d.p, hd.p, theta,
-                                   cnt, nullptr, nullptr, nullptr);
-        },
-        [&](const int* frp, int* fcol, double* fval) {
-            if (n)
-                hipLaunchKernelGGL(sa_filter_kernel<true>, dim3(grid1(n)), dim3(kT), 0, s, Av, Da, d.p, hd.p, theta,
-                                   nullptr, frp, fcol, fval);
-        });
-    const DCsr Fv = F.view();
-    // rho(D^-1 A_F): power steps in the max norm (exact maxima, the same on every partition)
-    double rho = 0.0;
-    {
-        DevBuf<double> x, y, hx;
-        DevBuf<unsigned long long> mx;
-        x.alloc((size_t)std::max(n, 1));
-        y.alloc((size_t)std::max(n, 1));
-        hx.alloc(1);
-        mx.alloc(1);
-        auto global_max = [&]() {
-            unsigned long long bits = 0;
-            HIP_CHECK(hipMemcpyAsync(&bits, mx.p, sizeof(bits), hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            double m;
-            std::memcpy(&m, &bits, sizeof(m));
-            return dist ? comm.allreduce_max(m) : m;
-        };
-        launch_uniform(s, n, lo, opt.seed + (uint64_t)level, x.p);
-        HIP_CHECK(hipMemsetAsync(mx.p, 0, sizeof(unsigned long long), s));
-        if (n) hipLaunchKernelGGL(max_abs_kernel, dim3(grid1(n)), dim3(kT), 0, s, n, x.p, mx.p);
-        const double m0 = global_max();
-        if (m0 > 0.0 && n) hipLaunchKernelGGL(div_scalar_kernel, dim3(grid1(n)), dim3(kT), 0, s, n, x.p, m0, x.p);
-        for (int it = 0; it < kSaRhoIters; ++it) {
-            if (dist) AH.forward(s, comm, x.p, hx);
-            HIP_CHECK(hipMemsetAsync(mx.p, 0, sizeof(unsigned long long), s));
-            if (n) hipLaunchKernelGGL(sa_power_kernel, dim3(grid1(n)), dim3(kT), 0, s, Fv, Da, x.p, hx.p, d.p, y.p, mx.p);
-            HIP_CHECK(hipGetLastError());
-            rho = global_max();
-            if (rho == 0.0) break;
-            if (n) hipLaunchKernelGGL(div_scalar_kernel, dim3(grid1(n)), dim3(kT), 0, s, n, y.p, rho, x.p);
-        }
-    }
-    const double omega = rho > 0.0 ? (4.0 / 3.0) / rho : 0.0;
-    tm.lap("  device filtered operator + rho");
-    // P = T - (omega / a_ii) A_F T on the device, on any number of ranks; one rank keeps it as
-    // the setup's image of P (transpose, Galerkin product)
-    static_assert(sizeof(long long) == sizeof(int64_t), "int64 columns");
+    T.dt.upload(tv.data(), tv.size());
+    T.hdt.alloc(1);
+    if (dist) H.AH.forward(L.s, comm, T.dt.p, T.hdt);
+}
+
+// the filtered operator A_F (r6): the diagonal + the strong couplings, weak ones lumped; returns
+// rho(D^-1 A_F)
+double filtered_operator_and_rho(LevelCtx& L, const SaHalo& H, DevS& F) {
+    hipStream_t s = L.s;
+    const int n = L.n;
+    const Dist Da = H.AH.dist(L.lo, n);
+    build_rows(L, F, sa_filter_kernel<false>, sa_filter_kernel<true>, L.Av, Da, H.d.p, H.hd.p, H.theta);
+    const DCsr Fv = view(L, F);
+    DevBuf<double> x, y, hx;
+    x.alloc((size_t)std::max(n, 1));
+    y.alloc((size_t)std::max(n, 1));
+    hx.alloc(1);
+    return power_iteration(s, L.comm, L.dist, n, L.lo, L.seed(), kSaRhoIters, x.p, y.p, [&](unsigned long long* mx) {
+        if (L.dist) H.AH.forward(s, L.comm, x.p, hx);
+        launch_rows(s, n, sa_power_kernel, Fv, Da, x.p, hx.p, H.d.p, y.p, mx);
+    });
+}
+
+// P = T - (omega / a_ii) A_F T on the device, on any number of ranks
+void smooth_P(LevelCtx& L, const SaHalo& H, const Aggregates& ag, const Tentative& T, const DevS& F, double omega,
+              DevRows<long long>& p) {
+    hipStream_t s = L.s;
+    const int n = L.n;
+    const Dist Da = H.AH.dist(L.lo, n);
+    const DCsr Fv = view(L, F);
     DevBuf<int> hagg, skey;
     DevBuf<double> sval;
     hagg.alloc(1);
-    if (dist) AH.forward(s, comm, agg.p, hagg);
-    const int64_t fnnz = F.nnz;
-    skey.alloc((size_t)std::max<int64_t>(fnnz, 1));
-    sval.alloc((size_t)std::max<int64_t>(fnnz, 1));
-    DevBuf<long long> pcnt, prp, pcol;
-    DevBuf<double> pval;
-    pcnt.alloc((size_t)n + 1);
-    HIP_CHECK(hipMemsetAsync(pcnt.p, 0, sizeof(long long) * pcnt.n, s));
-    if (n)
-        hipLaunchKernelGGL(sa_smooth_kernel<false>, dim3(grid1(n)), dim3(kT), 0, s, Fv, Da, agg.p, hagg.p, dt.p,
-                           hdt.p, d.p, omega, skey.p, sval.p, pcnt.p, nullptr, nullptr, nullptr);
-    prp.alloc((size_t)n + 1);
-    const int64_t pnnz = exclusive_scan64(s, pcnt.p, prp.p, n, tmp);
-    pcol.alloc((size_t)std::max<int64_t>(pnnz, 1));
-    pval.alloc((size_t)std::max<int64_t>(pnnz, 1));
-    if (n)
-        hipLaunchKernelGGL(sa_smooth_kernel<true>, dim3(grid1(n)), dim3(kT), 0, s, Fv, Da, agg.p, hagg.p, dt.p,
-                           hdt.p, d.p, omega, skey.p, sval.p, nullptr, prp.p, pcol.p, pval.p);
-    HIP_CHECK(hipGetLastError());
-    P = HostCSR();
-    P.n_global_rows = A.n_global_rows;
-    P.n_global_cols = na;
-    P.row_starts = A.row_starts;
-    P.col_starts = astarts;
-    P.rp.resize((size_t)n + 1);
-    P.col.resize((size_t)pnnz);
-    P.val.resize((size_t)pnnz);
-    copy_to_host(P.rp.data(), prp.p, sizeof(long long) * (n + 1), s);
-    copy_to_host(P.col.data(), pcol.p, sizeof(long long) * pnnz, nullptr);
-    copy_to_host(P.val.data(), pval.p, sizeof(double) * pnnz, nullptr);
-    if (imgs && !dist) {  // (N ranks: the transpose and SpGEMM build their own images of P)
-        std::unique_ptr<DevCsr> dp(new DevCsr());
-        dp->rp64 = std::move(prp);
-        dp->col64 = std::move(pcol);
-        dp->val = std::move(pval);
-        imgs->put(P, std::move(dp));
+    if (L.dist) H.AH.forward(s, L.comm, ag.agg.p, hagg);
+    skey.alloc((size_t)std::max<int64_t>(F.nnz, 1));
+    sval.alloc((size_t)std::max<int64_t>(F.nnz, 1));
+    build_rows(L, p, sa_smooth_kernel<false>, sa_smooth_kernel<true>, Fv, Da, ag.agg.p, hagg.p, T.dt.p, T.hdt.p,
+               H.d.p, omega, skey.p, sval.p);
+}
+
+// smoothed aggregation (host_setup.cpp strength_symmetric, mis2_aggregate, sa_prolongator)
+bool sa_level(LevelCtx& L, HostCSR& P, std::vector<int32_t>& split, SetupImages& im) {
+    SaHalo H;
+    Aggregates ag;
+    {
+        DevS S;  // the strength graph: the aggregation's alone
+        symmetric_strength(L, H, S);
+        L.tm.lap("  device strength");
+        mis2_aggregate(L, H, view(L, S), ag, split);
+        L.tm.lap("  device aggregation");
     }
-    tm.lap("  device smoothed prolongator");
+    Tentative T;
+    tentative_weights(L, H, split, ag.astarts, T);
+    L.tm.lap("  device tentative prolongator");
+    DevS F;
+    const double rho = filtered_operator_and_rho(L, H, F);
+    const double omega = rho > 0.0 ? (4.0 / 3.0) / rho : 0.0;
+    L.tm.lap("  device filtered operator + rho");
+    DevRows<long long> p;
+    smooth_P(L, H, ag, T, F, omega, p);
+    // one rank keeps P as the setup's image (N ranks: the transpose and SpGEMM build their own)
+    take_P(L, p, ag.astarts, P, L.dist ? nullptr : &im);
+    L.tm.lap("  device smoothed prolongator");
     return true;
+}
+
+}  // namespace
+
+double power_iteration(hipStream_t s, const HostComm& comm, bool dist, int n, int64_t first_gid, uint64_t seed,
+                       int iters, double* x, const double* y, const std::function<void(unsigned long long* m)>& step) {
+    DevBuf<unsigned long long> mx;
+    mx.alloc(1);
+    auto global_max = [&]() {
+        const unsigned long long bits = read_scalar(s, mx.p);
+        double m;
+        std::memcpy(&m, &bits, sizeof(m));
+        return dist ? comm.allreduce_max(m) : m;
+    };
+    launch_uniform(s, n, first_gid, seed, x);
+    HIP_CHECK(hipMemsetAsync(mx.p, 0, sizeof(unsigned long long), s));
+    launch_rows(s, n, max_abs_kernel, n, x, mx.p);
+    const double m0 = global_max();
+    if (m0 > 0.0) launch_rows(s, n, div_scalar_kernel, n, x, m0, x);
+    double lam = 0.0;
+    for (int it = 0; it < iters; ++it) {
+        HIP_CHECK(hipMemsetAsync(mx.p, 0, sizeof(unsigned long long), s));
+        step(mx.p);
+        HIP_CHECK(hipGetLastError());
+        lam = global_max();
+        if (lam == 0.0) break;
+        launch_rows(s, n, div_scalar_kernel, n, y, lam, x);
+    }
+    return lam;
+}
+
+// One level of the setup on the device: P and the integer split (C/F marker for RS-family
+// coarsening, aggregate id for SA), on any number of ranks.  Each rank works on its rows
+// with global column ids; the states of other ranks' points arrive through halo forwards
+// (pack on the device, the setup exchange on the host) -- exactly the synchronous rounds of
+// host_setup.cpp pmis_split / interp_classical / interp_ext_i / mis2_aggregate / sa_prolongator, so the
+// hierarchy is bit-identical to the host path's at every rank count.  Returns false for
+// Ruge-Stueben (the serial first pass stays on the host).
+bool level_setup_device(Context& ctx, const HostComm& comm, const HostCSR& A, const amg_options& opt,
+                        int level, HostCSR& P, std::vector<int32_t>& split, SetupImages* imgs, int64_t* ext_stats) {
+    if (ext_stats) ext_stats[0] = ext_stats[1] = 0;
+    // Ruge-Stueben (serial first pass): the host path
+    if (opt.coarsen == AMG_COARSEN_RS) return false;
+    if (comm.nranks == 1 && A.nrows() == 0) return false;
+    LevelCtx L(ctx.stream, comm, A, opt, level);
+    // A on the device: the setup's image (uploaded once, or left there by the previous level's
+    // Galerkin product); a caller without images gets this level's own
+    SetupImages local;
+    SetupImages& im = imgs ? *imgs : local;
+    DevCsr& DA = im.get(A);
+    AMG_CHECK(A.nrows() < INT_MAX && A.n_global_cols < INT_MAX, "device setup: level exceeds int32 indexing");
+    DA.ensure_rp32(L.s);
+    DA.ensure_col32(L.s);
+    L.Av = DCsr{DA.rp32.p, DA.col32.p, DA.val.p, L.n, L.lo};
+    if (opt.coarsen == AMG_COARSEN_PMIS) return pmis_level(L, P, split, im, ext_stats);
+    AMG_CHECK(opt.coarsen == AMG_COARSEN_SA, "unknown coarsening");
+    return sa_level(L, P, split, im);
 }
 
 namespace {
@@ -2151,16 +2169,15 @@ bool transpose_device_dist(Context& ctx, const HostComm& comm, const HostCSR& P,
         idx_out.alloc(nnz);
         rowof.alloc(nnz);
         recs.alloc(nnz);
-        hipLaunchKernelGGL(iota_kernel, dim3(grid1(nnz)), dim3(kT), 0, s, (int)nnz, idx_in.p);
-        if (n) hipLaunchKernelGGL(expand_rows_kernel, dim3(grid1(n)), dim3(kT), 0, s, dP.rp32.p, (int)n, rowof.p);
+        launch_rows(s, nnz, iota_kernel, (int)nnz, idx_in.p);
+        launch_rows(s, n, expand_rows_kernel, dP.rp32.p, (int)n, rowof.p);
         sort_pairs_stable(s, dP.col32.p, keys_out.p, idx_in.p, idx_out.p, (int)nnz, nc, tmp);
-        hipLaunchKernelGGL(transpose_records_kernel, dim3(grid1(nnz)), dim3(kT), 0, s, (int)nnz, keys_out.p, idx_out.p,
-                           rowof.p, dP.val.p, (long long)P.row_starts[me], recs.p);
+        launch_rows(s, nnz, transpose_records_kernel, (int)nnz, keys_out.p, idx_out.p, rowof.p, dP.val.p,
+                    (long long)P.row_starts[me], recs.p);
         std::vector<long long> bound(P.col_starts.begin() + 1, P.col_starts.end());
         dbound.upload(bound.data(), bound.size());
         doff.alloc((size_t)nr);
-        hipLaunchKernelGGL(owner_bounds_kernel, dim3(grid1(nr)), dim3(kT), 0, s, (int)nnz, keys_out.p, nr, dbound.p,
-                           doff.p);
+        launch_rows(s, nr, owner_bounds_kernel, (int)nnz, keys_out.p, nr, dbound.p, doff.p);
         HIP_CHECK(hipGetLastError());
         copy_to_host(off.data() + 1, doff.p, sizeof(long long) * nr, s);
         off[nr] = nnz;
@@ -2212,16 +2229,15 @@ bool transpose_device_dist(Context& ctx, const HostComm& comm, const HostCSR& P,
         key_out.alloc(rtot);
         idx_in.alloc(rtot);
         idx_out.alloc(rtot);
-        hipLaunchKernelGGL(record_rows_kernel, dim3(grid1(rtot)), dim3(kT), 0, s, (int)rtot, drec.p, (long long)lo, key.p);
-        hipLaunchKernelGGL(iota_kernel, dim3(grid1(rtot)), dim3(kT), 0, s, (int)rtot, idx_in.p);
+        launch_rows(s, rtot, record_rows_kernel, (int)rtot, drec.p, (long long)lo, key.p);
+        launch_rows(s, rtot, iota_kernel, (int)rtot, idx_in.p);
         sort_pairs_stable(s, key.p, key_out.p, idx_in.p, idx_out.p, (int)rtot, m_rows, tmp);
         rcol.alloc(rtot);
         rval.alloc(rtot);
-        hipLaunchKernelGGL(gather_records_kernel, dim3(grid1(rtot)), dim3(kT), 0, s, (int)rtot, idx_out.p, drec.p,
-                           rcol.p, rval.p);
+        launch_rows(s, rtot, gather_records_kernel, (int)rtot, idx_out.p, drec.p, rcol.p, rval.p);
         cntd.alloc((size_t)m_rows + 1);
         HIP_CHECK(hipMemsetAsync(cntd.p, 0, sizeof(int) * cntd.n, s));
-        hipLaunchKernelGGL(count_cols_kernel, dim3(grid1(rtot)), dim3(kT), 0, s, (int)rtot, key.p, cntd.p);
+        launch_rows(s, rtot, count_cols_kernel, (int)rtot, key.p, cntd.p);
         rrp.alloc((size_t)m_rows + 1);
         exclusive_scan(s, cntd.p, rrp.p, (int)m_rows, tmp);
         HIP_CHECK(hipGetLastError());
@@ -2249,50 +2265,29 @@ bool transpose_device(Context& ctx, const HostComm& comm, const HostCSR& P, Host
     hipStream_t s = ctx.stream;
     const int64_t n = P.nrows(), nnz = P.nnz(), nc = P.n_global_cols;
     if (nnz == 0 || n >= INT_MAX || nnz >= INT_MAX || nc >= INT_MAX) return false;
-    DevBuf<int> drp_up, dcol_up, keys_out, idx_in, idx_out, rowof, cnt, rrp;
-    DevBuf<double> dval_up;
+    DevBuf<int> keys_out, idx_in, idx_out, rowof, cnt, rrp;
     DevBuf<long long> rcol;
     DevBuf<double> rval;
     DevBuf<char> tmp;
-    const int *drp_p, *dcol_p;
-    const double* dval_p;
-    if (imgs) {  // P's image (left on the device by the level setup)
-        DevCsr& dP = imgs->get(P);
-        dP.ensure_rp32(s);
-        dP.ensure_col32(s);
-        drp_p = dP.rp32.p, dcol_p = dP.col32.p, dval_p = dP.val.p;
-    } else {
-        std::vector<int> rp(n + 1), col(nnz);
-#pragma omp parallel for schedule(static)
-        for (int64_t i = 0; i <= n; ++i) rp[i] = (int)P.rp[i];
-#pragma omp parallel for schedule(static)
-        for (int64_t k = 0; k < nnz; ++k) col[k] = (int)P.col[k];
-        drp_up.upload(rp.data(), rp.size());
-        dcol_up.upload(col.data(), col.size());
-        dval_up.upload(P.val.data(), P.val.size());
-        drp_p = drp_up.p, dcol_p = dcol_up.p, dval_p = dval_up.p;
-    }
+    SetupImages local;
+    DevCsr& dP = (imgs ? *imgs : local).get(P);  // P's image (left on the device by the level setup)
+    dP.ensure_rp32(s);
+    dP.ensure_col32(s);
+    const int *drp_p = dP.rp32.p, *dcol_p = dP.col32.p;
+    const double* dval_p = dP.val.p;
     keys_out.alloc(nnz);
     idx_in.alloc(nnz);
     idx_out.alloc(nnz);
     rowof.alloc(nnz);
-    hipLaunchKernelGGL(iota_kernel, dim3(grid1(nnz)), dim3(kT), 0, s, (int)nnz, idx_in.p);
-    hipLaunchKernelGGL(expand_rows_kernel, dim3(grid1(n)), dim3(kT), 0, s, drp_p, (int)n, rowof.p);
-    int bits = 1;
-    while (bits < 31 && (1ll << bits) < nc) ++bits;
-    size_t bytes = 0;
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, dcol_p, keys_out.p, idx_in.p, idx_out.p,
-                                                 (int)nnz, 0, bits, s));
-    tmp.alloc(bytes);
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.p, bytes, dcol_p, keys_out.p, idx_in.p, idx_out.p,
-                                                 (int)nnz, 0, bits, s));
+    launch_rows(s, nnz, iota_kernel, (int)nnz, idx_in.p);
+    launch_rows(s, n, expand_rows_kernel, drp_p, (int)n, rowof.p);
+    sort_pairs_stable(s, dcol_p, keys_out.p, idx_in.p, idx_out.p, (int)nnz, nc, tmp);
     rcol.alloc(nnz);
     rval.alloc(nnz);
-    hipLaunchKernelGGL(gather_transpose_kernel, dim3(grid1(nnz)), dim3(kT), 0, s, (int)nnz, idx_out.p,
-                       rowof.p, dval_p, rcol.p, rval.p);
+    launch_rows(s, nnz, gather_transpose_kernel, (int)nnz, idx_out.p, rowof.p, dval_p, rcol.p, rval.p);
     cnt.alloc((size_t)nc + 1);
     HIP_CHECK(hipMemsetAsync(cnt.p, 0, sizeof(int) * cnt.n, s));
-    hipLaunchKernelGGL(count_cols_kernel, dim3(grid1(nnz)), dim3(kT), 0, s, (int)nnz, dcol_p, cnt.p);
+    launch_rows(s, nnz, count_cols_kernel, (int)nnz, dcol_p, cnt.p);
     rrp.alloc((size_t)nc + 1);
     exclusive_scan(s, cnt.p, rrp.p, (int)nc, tmp);
     HIP_CHECK(hipGetLastError());
