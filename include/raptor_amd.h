@@ -162,6 +162,8 @@ typedef struct amg_matrix_info {
     int32_t row_seg;         /* segment length of the operator's row map: 8, 16 or 32 when its    *
                               * formats store the rows in an order of their own (the cycle's P_0,  *
                               * DESIGN.md 4.1; vectors, export and results are unchanged), 0: none */
+    int64_t mc_gs_bytes;     /* byte model of one multicolour GS sweep in its colour-major sliced   *
+                              * format (0: no colouring built)                      */
 } amg_matrix_info;
 int amg_par_csr_info(amg_matrix A, amg_matrix_info* info);
 
@@ -199,6 +201,7 @@ int amg_par_csr_export(amg_matrix A, int64_t* row_ptr, int64_t* col_global, doub
  *  - rejected: an output that overlaps b or x_prev without being the same pointer; for both
  *    hybrid GS calls an output that overlaps b at all (their sweeps read b in more than one
  *    pass);
+ *  - amg_par_csr_mc_gs: x is in-out (the sweep is in place) and overlaps no part of b;
  *  - solver calls: x (in-out) and b do not overlap.
  *
  * ParCSRMatrix::mult and the level kernels (rows a2-a5).  Each call performs the RCCL halo
@@ -218,6 +221,23 @@ int amg_par_csr_hybrid_gs(amg_matrix A, const double* x, const double* b, double
 /* the backward sweep (rows of each block in descending order; the V-cycle's post-smoother) */
 int amg_par_csr_hybrid_gs_backward(amg_matrix A, const double* x, const double* b, double* x_out,
                                    int64_t block);
+/* Multicolour Gauss-Seidel: a true Gauss-Seidel sweep in the order of a colouring
+ * that is defined on global ids, so the sweep is the same on every partition, bit for bit.
+ * amg_par_csr_colour builds the colouring of A's rows -- first-fit on the pattern of A + A^T in
+ * the order of the keys hash32(global id, seed) -- and the sweep's format; *n_colours (may be
+ * NULL) receives the colour count over all ranks.  Collective.  A later call replaces both.   */
+int amg_par_csr_colour(amg_matrix A, uint64_t seed, int32_t* n_colours);
+/* the colours of the local rows (n_local_rows entries); AMG_ERR_INVALID before amg_par_csr_colour */
+int amg_par_csr_colours(amg_matrix A, int32_t* out_local);
+/* readiness rounds the colouring took (a diagnostic: the depth of the key order's chains) */
+int amg_par_csr_colour_rounds(amg_matrix A, int32_t* rounds);
+/* One sweep in place: colours 0 .. C-1 (backward != 0: C-1 .. 0); every row i of the colour gets
+ * x_i = x_i + (1 / a_ii) (b_i - sum_k a_ik x_k), the sum in row order, reading the current x.
+ * x is in-out (n_local_cols doubles) and must not overlap b.  path: 0 = automatic, 1 = one launch
+ * per colour (on several ranks each preceded by the halo exchange of x), 2 = one workgroup with x
+ * in LDS -- AMG_ERR_INVALID on a distributed operator or beyond 16384 rows.  The paths give
+ * identical bits.  AMG_ERR_INVALID before amg_par_csr_colour.  Collective.                    */
+int amg_par_csr_mc_gs(amg_matrix A, double* x, const double* b, int32_t backward, int32_t path);
 /* C = A * B (ParCSRMatrix * ParCSRMatrix, row a10): the Galerkin SpGEMM kernel (one
  * wavefront per output row, LDS hash, canonical accumulation order => bit-identical to the
  * oracle).  A's column partition must equal B's row partition.  Collective.              */
@@ -234,6 +254,9 @@ int amg_par_csr_destroy(amg_matrix A);
 #define AMG_SMOOTH_HYBRID_GS 1
 #define AMG_SMOOTH_CHEBYSHEV 2  /* Chebyshev polynomial in D^-1 A on [f hi, hi], hi = 1.1 lambda_l
                                  * (DESIGN.md 3): SpMV-shaped passes only, partition independent */
+#define AMG_SMOOTH_MC_GS 3      /* multicolour Gauss-Seidel: forward sweeps before, backward sweeps
+                                 * after the coarse correction; colourings of seed + level
+                                 * (DESIGN.md 3): partition independent, a symmetric cycle      */
 #define AMG_INTERP_CLASSICAL 0  /* RS / PMIS: distance-one classical (modified) interpolation  */
 #define AMG_INTERP_EXT_I 1      /* RS / PMIS: distance-two extended+i with P_max truncation    *
                                  * (any number of ranks; PMIS: built on the GPU) */
@@ -307,6 +330,9 @@ int amg_solver_level_ext_stats(amg_solver S, int32_t level, int64_t* scratch_row
  * from the seeded vector of seed + l (the same on every partition).  AMG_ERR_INVALID for the
  * coarsest level or another smoother. */
 int amg_solver_level_eig(amg_solver S, int32_t level, double* lambda);
+/* AMG_SMOOTH_MC_GS: colours of level l's ordering and whether its sweeps run in one workgroup
+ * (1) or as a launch per colour (0).  AMG_ERR_INVALID for the coarsest level or another smoother. */
+int amg_solver_level_colours(amg_solver S, int32_t level, int32_t* n_colours, int32_t* one_workgroup);
 /* One V-cycle x <- cycle(x, b) (ParMultilevel::cycle). */
 int amg_solver_cycle(amg_solver S, double* x, const double* b);
 /* ParMultilevel::solve: r0 = ||b-Ax||; up to max_iter cycles until ||r||/r0 < tol.

@@ -136,6 +136,25 @@ public:
         check(backward ? amg_par_csr_hybrid_gs_backward(h_, x, b, x_out, block)
                        : amg_par_csr_hybrid_gs(h_, x, b, x_out, block));
     }
+    // multicolour Gauss-Seidel (raptor_amd.h): colour() builds the ordering of the rows (the same
+    // on every partition) and the sweep's format and returns the colour count; mc_gs() is one
+    // sweep in place on x (path 0 automatic, 1 a launch per colour, 2 one workgroup); x must not
+    // overlap b
+    int32_t colour(uint64_t seed = 0x5EED) {
+        int32_t n = 0;
+        check(amg_par_csr_colour(h_, seed, &n));
+        return n;
+    }
+    std::vector<int32_t> colours() const {
+        amg_matrix_info inf;
+        check(amg_par_csr_info(h_, &inf));
+        std::vector<int32_t> c((size_t)inf.n_local_rows);
+        check(amg_par_csr_colours(h_, c.data()));
+        return c;
+    }
+    void mc_gs(double* x, const double* b, bool backward = false, int32_t path = 0) const {
+        check(amg_par_csr_mc_gs(h_, x, b, backward ? 1 : 0, path));
+    }
     double residual_norm(const double* x, const double* b) const {
         double v = 0.0;
         check(amg_par_csr_residual_norm(h_, x, b, &v));
@@ -200,6 +219,14 @@ public:
         double v = 0.0;
         check(amg_solver_level_eig(h_, level, &v));
         return v;
+    }
+    // AMG_SMOOTH_MC_GS: colours of the level's ordering; *one_workgroup: its sweeps run in one
+    // workgroup (throws for the coarsest level or another smoother)
+    int32_t level_colours(int level, bool* one_workgroup = nullptr) const {
+        int32_t n = 0, w = 0;
+        check(amg_solver_level_colours(h_, level, &n, &w));
+        if (one_workgroup) *one_workgroup = w != 0;
+        return n;
     }
     // true: level's split and P came from the device setup path (not the host fallback)
     bool level_setup_on_device(int level) const {

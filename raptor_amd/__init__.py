@@ -43,6 +43,7 @@ from ._lib import (  # noqa: F401  (re-exported constants)
     AMG_SMOOTH_CHEBYSHEV,
     AMG_SMOOTH_HYBRID_GS,
     AMG_SMOOTH_JACOBI,
+    AMG_SMOOTH_MC_GS,
     AMG_STENCIL_5PT,
     AMG_STENCIL_7PT,
     AMG_STENCIL_27PT,
@@ -485,6 +486,34 @@ class ParCSRMatrix:
         check(fn(self.h, _ptr(x), _ptr(b), _ptr(x_out), int(block)))
         return x_out
 
+    def colour(self, seed=0x5EED) -> int:
+        """Build the multicolour ordering of the rows (first-fit on the pattern of A + A^T in the
+        order of the keys hash32(global id, seed); the same on every partition) and the sweep's
+        format; returns the number of colours over all ranks.  Collective."""
+        n = C.c_int32()
+        check(lib().amg_par_csr_colour(self.h, C.c_uint64(seed), C.byref(n)))
+        return n.value
+
+    def colours(self):
+        """The colours of the local rows (after ``colour``)."""
+        out = np.empty(self.local_rows, np.int32)
+        check(lib().amg_par_csr_colours(self.h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def colour_rounds(self) -> int:
+        """Readiness rounds the last ``colour`` took."""
+        n = C.c_int32()
+        check(lib().amg_par_csr_colour_rounds(self.h, C.byref(n)))
+        return n.value
+
+    def mc_gs(self, x, b, backward=False, path=0):
+        """One multicolour Gauss-Seidel sweep in place on ``x`` (after ``colour``): colours in
+        ascending order, descending when ``backward``.  ``path``: 0 automatic, 1 a launch per
+        colour, 2 one workgroup (one rank, at most 16384 rows); the bits are the same.  ``x``
+        must not overlap ``b``."""
+        check(lib().amg_par_csr_mc_gs(self.h, _ptr(x), _ptr(b), 1 if backward else 0, int(path)))
+        return x
+
     def matmat(self, B: "ParCSRMatrix") -> "ParCSRMatrix":
         """C = self * B on the GPU (Galerkin SpGEMM kernel; collective)."""
         h = C.c_void_p()
@@ -607,7 +636,9 @@ class ParMultilevel:
     """AMG hierarchy + V-cycle (RAPtor ParMultilevel analogue).
 
     ``coarsen``: "rs" (serial Ruge-Stueben), "pmis", or "sa" (smoothed aggregation over MIS(2)
-    aggregates).  ``smoother``: "jacobi", "hybrid_gs" or "chebyshev" (a polynomial of degree
+    aggregates).  ``smoother``: "jacobi", "hybrid_gs", "mc_gs" (multicolour Gauss-Seidel: true GS
+    sweeps in the order of a colouring defined on global ids, forward before and backward after
+    the coarse correction; symmetric and partition independent) or "chebyshev" (a polynomial of degree
     ``cheby_degree`` in D^-1 A that damps [``cheby_fraction`` hi, hi], hi = 1.1 x the level's
     eigenvalue estimate; symmetric and partition independent).  ``interp`` (RS / PMIS): "classical"
     (distance one) or "ext+i" (distance two, ``p_max`` entries kept per row; any number of
@@ -618,7 +649,7 @@ class ParMultilevel:
     _COARSEN = {"rs": AMG_COARSEN_RS, "pmis": AMG_COARSEN_PMIS, "sa": AMG_COARSEN_SA}
     _INTERP = {"classical": AMG_INTERP_CLASSICAL, "ext+i": AMG_INTERP_EXT_I}
     _SMOOTH = {"jacobi": AMG_SMOOTH_JACOBI, "hybrid_gs": AMG_SMOOTH_HYBRID_GS,
-               "chebyshev": AMG_SMOOTH_CHEBYSHEV}
+               "chebyshev": AMG_SMOOTH_CHEBYSHEV, "mc_gs": AMG_SMOOTH_MC_GS}
 
     def __init__(self, coarsen="pmis", smoother="jacobi", strong_threshold=None,
                  jacobi_omega=2.0 / 3.0, pre_sweeps=1, post_sweeps=1, max_levels=25,
@@ -681,6 +712,14 @@ class ParMultilevel:
         v = C.c_double()
         check(lib().amg_solver_level_eig(self.h, int(level), C.byref(v)))
         return v.value
+
+    def level_colours(self, level: int) -> dict:
+        """smoother="mc_gs": ``n_colours`` of the level's ordering and ``one_workgroup`` (1: its
+        sweeps run in one workgroup, 0: a launch per colour).  Raises for the coarsest level or
+        another smoother."""
+        n, w = C.c_int32(), C.c_int32()
+        check(lib().amg_solver_level_colours(self.h, int(level), C.byref(n), C.byref(w)))
+        return {"n_colours": n.value, "one_workgroup": w.value}
 
     def level_setup_on_device(self, level: int) -> int:
         """1 if the level's split and P were built by the device setup path, 0 if the host

@@ -14,6 +14,7 @@ AMG_OK = 0
 AMG_STENCIL_5PT, AMG_STENCIL_7PT, AMG_STENCIL_27PT = 0, 1, 2
 AMG_COARSEN_RS, AMG_COARSEN_PMIS, AMG_COARSEN_SA = 0, 1, 2
 AMG_SMOOTH_JACOBI, AMG_SMOOTH_HYBRID_GS, AMG_SMOOTH_CHEBYSHEV = 0, 1, 2
+AMG_SMOOTH_MC_GS = 3
 AMG_INTERP_CLASSICAL, AMG_INTERP_EXT_I = 0, 1
 AMG_PRESET_PMIS_JACOBI, AMG_PRESET_RS_JACOBI, AMG_PRESET_SA_HYBRID_GS = 0, 1, 2
 AMG_REORDER_RCM = 1
@@ -84,6 +85,7 @@ class MatrixInfo(C.Structure):
         ("gs_chain_maxw", C.c_int32),
         ("deferred", C.c_int32),
         ("row_seg", C.c_int32),
+        ("mc_gs_bytes", C.c_int64),
     ]
 
 
@@ -141,6 +143,10 @@ SIGNATURES = {
     "amg_par_csr_chebyshev_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f64, _f64]),
     "amg_par_csr_hybrid_gs": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),
     "amg_par_csr_hybrid_gs_backward": (C.c_int, [_vp, _vp, _vp, _vp, _i64]),
+    "amg_par_csr_colour": (C.c_int, [_vp, C.c_uint64, C.POINTER(_i32)]),
+    "amg_par_csr_colours": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "amg_par_csr_colour_rounds": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "amg_par_csr_mc_gs": (C.c_int, [_vp, _vp, _vp, _i32, _i32]),
     "amg_par_csr_residual_norm": (C.c_int, [_vp, _vp, _vp, _pf64]),
     "amg_par_csr_matmat": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "amg_par_csr_destroy": (C.c_int, [_vp]),
@@ -151,6 +157,7 @@ SIGNATURES = {
     "amg_solver_level_matrix": (C.c_int, [_vp, _i32, _i32, C.POINTER(_vp)]),
     "amg_solver_level_split": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
     "amg_solver_level_eig": (C.c_int, [_vp, _i32, C.POINTER(_f64)]),
+    "amg_solver_level_colours": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "amg_solver_level_setup_device": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
     "amg_solver_level_ext_stats": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i64)]),
     "amg_solver_cycle": (C.c_int, [_vp, _vp, _vp]),

@@ -386,6 +386,7 @@ int amg_par_csr_info(amg_matrix A, amg_matrix_info* info) {
         info->gs_split = m.gs.block > 0 && m.gs.split.on ? 1 : 0;
         info->gs_chain_maxw = info->gs_split ? m.gs.split.cmaxw[0] | m.gs.split.cmaxw[1] << 16 : 0;
         info->row_seg = m.row_seg;
+        info->mc_gs_bytes = m.mc.built ? m.mc.bytes : 0;
     });
 }
 
@@ -548,6 +549,50 @@ int amg_par_csr_hybrid_gs_backward(amg_matrix A, const double* x, const double* 
         A->m->ensure_built();
         release_setup_image(*A->m);
         par_hybrid_gs(*A->m, x, b, xo, block, true);
+    });
+}
+
+int amg_par_csr_colour(amg_matrix A, uint64_t seed, int32_t* n_colours) {
+    return guard([&] {
+        AMG_CHECK(A, "null matrix");
+        DevMatrix& M = *A->m;
+        AMG_CHECK(M.square, "colour: a square matrix");
+        set_device(*M.ctx);
+        HIP_CHECK(hipStreamSynchronize(M.ctx->stream));
+        M.ensure_built();
+        release_setup_image(M);
+        static const HostComm serial;  // a replicated operator is whole here
+        M.build_mc_gs(colour_device(*M.ctx, M.replicated ? serial : M.ctx->host, M.host_image(), seed), seed);
+        if (n_colours) *n_colours = M.mc.colouring.n_colours;
+    });
+}
+
+int amg_par_csr_colours(amg_matrix A, int32_t* out) {
+    return guard([&] {
+        AMG_CHECK(A, "null matrix");
+        AMG_CHECK(A->m->mc.built, "colours: the operator has no colouring (amg_par_csr_colour)");
+        const std::vector<int32_t>& c = A->m->mc.colouring.colour;
+        AMG_CHECK(out || c.empty(), "null argument");
+        std::copy(c.begin(), c.end(), out);
+    });
+}
+
+int amg_par_csr_colour_rounds(amg_matrix A, int32_t* rounds) {
+    return guard([&] {
+        AMG_CHECK(A && rounds, "null argument");
+        AMG_CHECK(A->m->mc.built, "colour_rounds: the operator has no colouring (amg_par_csr_colour)");
+        *rounds = A->m->mc.colouring.rounds;
+    });
+}
+
+int amg_par_csr_mc_gs(amg_matrix A, double* x, const double* b, int32_t backward, int32_t path) {
+    return guard([&] {
+        AMG_CHECK(A, "null matrix");
+        // x is in-out and read by other rows' lanes; b is read once per row
+        check_vectors("mc_gs", {"x", x, A->m->n_cols_local, 0}, {{"b", b, A->m->n_rows, kNoOverlap}});
+        set_device(*A->m->ctx);
+        release_setup_image(*A->m);
+        par_mc_gs(*A->m, x, b, backward != 0, path);
     });
 }
 
@@ -732,6 +777,17 @@ int amg_solver_level_eig(amg_solver S, int32_t l, double* lambda) {
         AMG_CHECK(S->s.opt.smoother == AMG_SMOOTH_CHEBYSHEV, "eigenvalue estimates exist under the Chebyshev smoother");
         AMG_CHECK(l >= 0 && l + 1 < (int32_t)S->s.levels.size(), "level has no smoother (the coarsest level is solved)");
         *lambda = S->s.cheby[l].lambda;
+    });
+}
+
+int amg_solver_level_colours(amg_solver S, int32_t l, int32_t* n_colours, int32_t* one_workgroup) {
+    return guard([&] {
+        AMG_CHECK(S && n_colours && one_workgroup, "null argument");
+        AMG_CHECK(S->s.opt.smoother == AMG_SMOOTH_MC_GS, "colourings exist under the multicolour GS smoother");
+        AMG_CHECK(l >= 0 && l + 1 < (int32_t)S->s.levels.size(), "level has no smoother (the coarsest level is solved)");
+        const DevMatrix& A = S->s.Amat(l);
+        *n_colours = A.mc.colouring.n_colours;
+        *one_workgroup = A.mc_one_wg_fits() && A.n_rows <= mc_wg_rows() ? 1 : 0;
     });
 }
 

@@ -221,6 +221,16 @@ bool level_setup_device(Context& ctx, const HostComm& comm, const HostCSR& A, co
                         int64_t* ext_stats = nullptr);
 bool transpose_device(Context& ctx, const HostComm& comm, const HostCSR& P, HostCSR& R,
                       SetupImages* imgs = nullptr);
+// Multicolour ordering of a square operator's rows (setup_device.hip beside the
+// PMIS split): first-fit colours in hash-key order on the pattern of A u A^T, the same on every
+// partition.  colour: per local row; n_colours: over all ranks; rounds: readiness rounds taken
+struct Colouring {
+    std::vector<int32_t> colour;
+    int32_t n_colours = 0;
+    int32_t rounds = 0;
+};
+Colouring colour_device(Context& ctx, const HostComm& comm, const HostCSR& A, uint64_t seed,
+                        SetupImages* imgs = nullptr);
 // coarse-operator drop tolerance (host_setup.cpp sparsify) on A's device image (one rank; the
 // host sparsify otherwise); the result is registered in imgs
 HostCSR sparsify_device(Context& ctx, const HostComm& comm, const HostCSR& A, double tau, SetupImages* imgs);
@@ -366,6 +376,34 @@ struct GsFormat {
     int norm_parts() const { return n_slabs + kNormParts * tpl.n_blk; }
 };
 
+// Multicolour Gauss-Seidel: the rows colour-major (rows of a colour ascending),
+// each colour cut into slices.  A lane colour (rows average <= kMcSlice entries) has slices of
+// <= 64 rows, sliced-ELL and column-major like GsFormat (entry k of lane l at (off + k) * 64 + l);
+// a wave colour has one row per slice, its entries contiguous from off * 64, padded to whole 64s.
+// col -1 = padding (masked, never multiplied).  dinv = 1 / a_ii, by position in the row list.
+constexpr int kMcSlice = 64;
+constexpr int kMcWgThreads = 1024;      // the one-workgroup sweep: 16 waves
+constexpr int kMcWgCapacity = 16384;    // its x in LDS: 128 KiB of the CU's 160
+// rows up to which the automatic path takes the one-workgroup sweep: its capacity.  Measured
+// (profiles/mc_gs/timeline_wg*.json): in a captured cycle the one-workgroup sweeps
+// of levels of 692 ... 14,069 rows took 0.65 - 0.75 of the time of their per-colour launches
+constexpr int kMcWgRows = kMcWgCapacity;
+struct McGsFormat {
+    bool built = false;
+    uint64_t seed = 0;              // the colouring's hash seed
+    Colouring colouring;
+    std::vector<int> cslice_host;   // per colour: first slice (n_colours + 1)
+    std::vector<uint8_t> wave_host; // per colour: 1 = a wave per row
+    DevBuf<int4> slices;            // {first position in rows, rows, offset / 64, width}
+    DevBuf<int> cslice;             // cslice_host on the device
+    DevBuf<uint8_t> wave;           // wave_host on the device
+    DevBuf<int> rows, col;
+    DevBuf<double> val, dinv;
+    int n_slices = 0;
+    int64_t cells = 0;
+    int64_t bytes = 0;  // byte model of one sweep
+};
+
 // ParCSRMatrix on the device: rank-local rows, columns renumbered [local | halo].
 struct DevMatrix {
     Context* ctx = nullptr;
@@ -434,6 +472,11 @@ struct DevMatrix {
     GsFormat gs;
     void ensure_gs_ell();
     void ensure_gs_pass(int d);  // gs.split.old[d], built on first use (ensure_gs_blocks: d = 1)
+    // multicolour GS (mc_gs.hip): the format of a colouring of this operator's rows
+    McGsFormat mc;
+    void build_mc_gs(Colouring&& c, uint64_t seed);
+    // the one-workgroup sweep applies: no halo exchange and the rows fit its LDS
+    bool mc_one_wg_fits() const;
     int64_t csr_fmt_bytes = 0;  // spmv_fmt_bytes with templates off (AMG_KERNEL_VARIANT)
     // storage format the level kernels use (AMG_FORMAT_*, amg_par_csr_set_format):
     // AUTO = templates + CSR blocks (default), BLOCKS = CSR blocks only, CSR = plain CSR
@@ -616,6 +659,12 @@ void par_hybrid_gs(DevMatrix& A, const double* x, const double* b, double* y, in
                    bool backward = false, double* partial = nullptr);
 // the forward sweep from x0 = 0 (zeroed by the caller): the split form skips its old-value pass
 void par_hybrid_gs_from_zero(DevMatrix& A, const double* x0, const double* b, double* y, int64_t block);
+// One multicolour GS sweep in place on x: colours ascending, or descending when
+// backward; on several ranks every colour's launch follows a halo exchange of x.  path 0: the
+// one-workgroup sweep up to kMcWgRows rows where it applies, 1: a launch per colour, 2: one
+// workgroup (AMG_ERR_INVALID where it does not apply).  The paths give the same bits
+void par_mc_gs(DevMatrix& A, double* x, const double* b, bool backward, int path);
+int mc_wg_rows();  // kMcWgRows, or the AMG_MC_GS_WG_ROWS override
 // Norm plumbing: a mode-NORM level kernel leaves per-block partial sums of (b - Ax)^2 in
 // NormSink::partial; norm_finish() reduces them (fixed order), combines ranks (RCCL
 // allgather, rank order) and appends sqrt to hist[*counter] -- all on the device.
@@ -724,6 +773,8 @@ struct Solver {
     };
     std::vector<Cheby> cheby;
     void setup_cheby();
+    // AMG_SMOOTH_MC_GS: colours every smoothed level (seed + l) and builds its format
+    void setup_mc_gs();
     bool jacobi_like() const { return opt.smoother == AMG_SMOOTH_JACOBI || opt.smoother == AMG_SMOOTH_CHEBYSHEV; }
     // omega of the Jacobi-shaped first step of level l's smoother
     double omega0(size_t l) const { return opt.smoother == AMG_SMOOTH_CHEBYSHEV ? cheby[l].w0 : opt.jacobi_omega; }

@@ -239,7 +239,7 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
     AMG_CHECK(o.pre_sweeps >= 0 && o.post_sweeps >= 0, "negative sweep count");
     AMG_CHECK(o.max_levels >= 1, "max_levels must be >= 1");
     AMG_CHECK(o.smoother == AMG_SMOOTH_JACOBI || o.smoother == AMG_SMOOTH_HYBRID_GS ||
-                  o.smoother == AMG_SMOOTH_CHEBYSHEV, "bad smoother");
+                  o.smoother == AMG_SMOOTH_CHEBYSHEV || o.smoother == AMG_SMOOTH_MC_GS, "bad smoother");
     if (o.smoother == AMG_SMOOTH_CHEBYSHEV) {  // read only here: other callers may leave them zero
         AMG_CHECK(o.cheby_degree >= 1 && o.cheby_degree <= 16, "cheby_degree must be 1 .. 16");
         AMG_CHECK(o.cheby_fraction > 0.0 && o.cheby_fraction < 1.0, "cheby_fraction must lie in (0, 1)");
@@ -301,6 +301,15 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
     const size_t maxl = (size_t)std::max(opt.max_levels, 1) + 1;
     std::vector<std::unique_ptr<DevMatrix>> preA(maxl), preP(maxl), preR(maxl), preAc(maxl), prePc(maxl), preRc(maxl);
     const bool hgs = opt.smoother == AMG_SMOOTH_HYBRID_GS;
+    // multicolour GS: a level is coloured while the setup's images hold its operator (one rank:
+    // level 0 before the hierarchy, A_{l+1} when level l is done); the levels left over are
+    // coloured on their own once the operators are built (setup_mc_gs)
+    const bool mcgs = opt.smoother == AMG_SMOOTH_MC_GS;
+    std::vector<std::unique_ptr<Colouring>> mc_pre(maxl);
+    auto mc_colour = [&](size_t l, const HostCSR& M) {
+        if (mcgs && im && comm.nranks == 1)
+            mc_pre[l].reset(new Colouring(colour_device(*ctx, comm, M, opt.seed + (uint64_t)l, im)));
+    };
     // cycle order: the brick order of level l + 1 is fixed once R_l exists; the operators that
     // touch a permuted level are built as cycle-order copies (their hierarchy-order formats wait
     // for a caller that asks for them: DevMatrix::defer)
@@ -324,7 +333,12 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
     };
     // a level operator's hybrid-GS structures: l1 diagonals, slabs, templates,
     // the split sweep's old-value pass (built by ensure_gs_blocks), level 0's sliced ELL
-    auto gs_build = [this](DevMatrix& Al, int l) {
+    auto gs_build = [this, mcgs, &mc_pre](DevMatrix& Al, int l) {
+        if (mcgs) {  // the format of the level's colouring (the coarsest level's goes unused)
+            if (mc_pre[l]) Al.build_mc_gs(std::move(*mc_pre[l]), opt.seed + (uint64_t)l);
+            mc_pre[l].reset();
+            return;
+        }
         Al.ensure_gs_blocks(opt.gs_block);
         // level 0's norm-carrying forward sweep runs the one-kernel form, inside captured
         // cycles: its sliced ELL is built now even where the other sweeps run split
@@ -345,9 +359,10 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
         if (overlap) {
             worker.reset(new FormatWorker(ctx->device));
             worker2.reset(new FormatWorker(ctx->device));
-            if (hgs) {
+            if (hgs || mcgs) {
                 gs_worker.reset(new FormatWorker(ctx->device));
                 DevMatrix* a0 = &A;
+                mc_colour(0, A.host);
                 gs_worker->push([gs_build, a0] { gs_build(*a0, 0); });
             }
             done = [&](int l) {
@@ -369,6 +384,7 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
                 // (r5: P_l and R_l on a second format worker beside A_{l+1})
                 co.next((size_t)l, H.levels[l].R, opt, comm);
                 const size_t a = (size_t)l + 1, p = (size_t)l;
+                mc_colour(a, H.levels[a].A);
                 if (co.any(a)) {
                     const HostCSR* M = &H.levels[a].A;
                     worker->push([&, a, M] { preAc[a] = copy(*M, co.perm[a], co.inv[a]); });
@@ -532,6 +548,25 @@ void Solver::setup(DevMatrix& A, const amg_options& o) {
         setup_cheby();
         tm.lap("Chebyshev eigenvalue estimates");
     }
+    if (mcgs) {
+        setup_mc_gs();
+        tm.lap("multicolour GS colourings and formats");
+    }
+}
+
+// Every smoothed level that the overlapped setup has not coloured already: the colouring of
+// seed + l (collective on a distributed level; a replicated level is whole on every rank and
+// coloured as one rank's) and its format
+void Solver::setup_mc_gs() {
+    static const HostComm serial;
+    for (size_t l = 0; l + 1 < levels.size(); ++l) {
+        DevMatrix& A = Amat(l);
+        A.ensure_built();
+        // (level 0 is the caller's matrix: a colouring of another seed is replaced)
+        if (A.mc.built && A.mc.seed == opt.seed + (uint64_t)l) continue;
+        A.build_mc_gs(colour_device(*ctx, A.replicated ? serial : ctx->host, A.host_image(), opt.seed + (uint64_t)l),
+                      opt.seed + (uint64_t)l);
+    }
 }
 
 namespace {
@@ -634,6 +669,15 @@ void Solver::ensure_hist(int32_t n) {
 void Solver::smooth(size_t l, double*& x, const double* b, double*& tmp, bool x_zero,
                     bool with_norm, bool post, bool x0_in_t) {
     DevMatrix& A = CA(l);
+    if (opt.smoother == AMG_SMOOTH_MC_GS) {
+        // in place: forward before the coarse correction, backward after it.  From zero the
+        // sweep runs as it is on a zeroed x (no shortcut: the bits of the definition)
+        AMG_ASSERT(!with_norm && !x0_in_t);
+        if (x_zero) launch_zero(ctx->stream, A.n_rows, x);
+        par_mc_gs(A, x, b, post, 0);
+        mark(l, post ? "post-smooth mc sweep" : x_zero ? "pre-smooth mc sweep from 0" : "pre-smooth mc sweep");
+        return;
+    }
     if (opt.smoother == AMG_SMOOTH_CHEBYSHEV) {
         // one application of the degree-m polynomial: step 0 is a Jacobi step with omega = w0 on
         // Jacobi's paths; step k >= 1 writes x_{k+1} over x_{k-1} (y aliases xprev), so the two
@@ -1423,7 +1467,8 @@ int64_t Solver::bytes_per_cycle(size_t l) const {
     b += spmv_bytes(me.CP(l)) + 8 * n;                    // interpolation (reads x)
     b += opt.post_sweeps * (jac + later);
     sweeps += opt.post_sweeps;
-    if (sweeps * sweep_steps() % 2 == 1) b += 16 * n;     // copy back
+    // (multicolour GS sweeps in place: priced as a GS sweep, never copied back)
+    if (opt.smoother != AMG_SMOOTH_MC_GS && sweeps * sweep_steps() % 2 == 1) b += 16 * n;  // copy back
     return b;
 }
 
@@ -1438,8 +1483,11 @@ int64_t Solver::stored_bytes_per_cycle(size_t l) const {
     const DevMatrix& A = me.CA(l);  // the operators the cycle runs
     const int64_t n = A.n_rows;
     if (l + 1 == levels.size()) return 8 * coarse_n * n + 8 * coarse_n + 8 * n;
-    const bool gs = opt.smoother == AMG_SMOOTH_HYBRID_GS;
-    const int64_t sweep = gs ? A.gs.bytes : A.mode_bytes(KM_JACOBI);
+    // multicolour GS: its own format's byte model per sweep, in place (no fused sweep from zero,
+    // no copy back)
+    const bool mc = opt.smoother == AMG_SMOOTH_MC_GS;
+    const bool gs = opt.smoother == AMG_SMOOTH_HYBRID_GS || mc;
+    const int64_t sweep = mc ? A.mc.bytes : gs ? A.gs.bytes : A.mode_bytes(KM_JACOBI);
     const int64_t later = (sweep_steps() - 1) * A.mode_bytes(KM_CHEBY);  // Chebyshev steps k >= 1
     int64_t b = 0;
     bool zero = l > 0;
@@ -1449,7 +1497,7 @@ int64_t Solver::stored_bytes_per_cycle(size_t l) const {
     const bool j0 = !gs && Rup && (int)l != rep_level && Rup->format != AMG_FORMAT_CSR &&
                     !Rup->tpl_on();
     // a split GS sweep from zero is its chain walk alone (par_hybrid_gs_from_zero)
-    const int64_t sweep0 = gs && A.gs.split.on ? sweep - A.gs.split.old[1]->mode_bytes(KM_RESID) - 8 * n : sweep;
+    const int64_t sweep0 = gs && !mc && A.gs.split.on ? sweep - A.gs.split.old[1]->mode_bytes(KM_RESID) - 8 * n : sweep;
     for (int k = 0; k < opt.pre_sweeps; ++k, ++sweeps) {
         if (zero && !gs) b += (j0 ? 16 : 24) * n;  // omega * dinv * b
         else b += (zero ? sweep0 : sweep) + (zero ? 8 * n : 0);  // (zero fill of x first)
@@ -1462,7 +1510,7 @@ int64_t Solver::stored_bytes_per_cycle(size_t l) const {
     b += me.CP(l).mode_bytes(KM_SPMV_ADD);
     b += opt.post_sweeps * (sweep + later);
     sweeps += opt.post_sweeps;
-    if (sweeps * sweep_steps() % 2 == 1) b += 16 * n;  // copy back
+    if (!mc && sweeps * sweep_steps() % 2 == 1) b += 16 * n;  // copy back
     return b;
 }
 

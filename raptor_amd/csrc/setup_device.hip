@@ -253,6 +253,72 @@ __global__ void pmis_fpass_kernel(DCsr S, Dist D, int* cf, const int* hcf, unsig
     atomicAdd(nu, 1ull);
 }
 
+// ---- multicolour ordering ---------------------------------------------------
+// key = hash32(global id); u precedes v iff key(u) > key(v), or the keys tie and u < v
+__global__ void colour_init_kernel(int n, int lo, unsigned long long seed, unsigned* key, int* colour) {
+    const int i = blockIdx.x * kT + threadIdx.x;
+    if (i >= n) return;
+    key[i] = dhash32(lo + i, seed);
+    colour[i] = -1;
+}
+
+// One readiness round of the first-fit colouring on the pattern of A u A^T (rows of A, local
+// dependents tcol, off-rank dependents ecol; the diagonal and repeated neighbours are harmless):
+// an uncoloured row whose preceding neighbours are all coloured takes the smallest colour none
+// of them uses (64 colours per pass over its neighbours).  Reads the previous round's colours
+// only; newc[i] = the colour taken, -1: not this round
+__global__ void colour_select_kernel(DCsr A, Dist D, const int* trp, const int* tcol, const int* erp,
+                                     const int* ecol, const unsigned* key, const unsigned* hkey, const int* colour,
+                                     const int* hcolour, int* newc) {
+    const int i = blockIdx.x * kT + threadIdx.x;
+    if (i >= A.n) return;
+    newc[i] = -1;
+    if (colour[i] >= 0) return;
+    const unsigned ki = key[i];
+    const int gi = A.lo + i;
+    // colour of neighbour g if it precedes i (-1: uncoloured), -2 if it does not precede
+    auto before = [&](int g) {
+        if (g == gi) return -2;
+        const int l = D.loc(g);
+        const unsigned kj = l >= 0 ? key[l] : hkey[-l - 1];
+        if (!(kj > ki || (kj == ki && g < gi))) return -2;
+        return l >= 0 ? colour[l] : hcolour[-l - 1];
+    };
+    bool ready = true;
+    for (int k = A.rp[i]; k < A.rp[i + 1] && ready; ++k) ready = before(A.col[k]) != -1;
+    for (int t = trp[i]; t < trp[i + 1] && ready; ++t) ready = before(tcol[t]) != -1;
+    if (erp)
+        for (int t = erp[i]; t < erp[i + 1] && ready; ++t) ready = before(ecol[t]) != -1;
+    if (!ready) return;
+    for (int base = 0;; base += 64) {
+        unsigned long long used = 0;
+        auto take = [&](int g) {
+            const int c = before(g) - base;
+            if (c >= 0 && c < 64) used |= 1ull << c;
+        };
+        for (int k = A.rp[i]; k < A.rp[i + 1]; ++k) take(A.col[k]);
+        for (int t = trp[i]; t < trp[i + 1]; ++t) take(tcol[t]);
+        if (erp)
+            for (int t = erp[i]; t < erp[i + 1]; ++t) take(ecol[t]);
+        if (~used) {
+            newc[i] = base + __ffsll((long long)~used) - 1;
+            return;
+        }
+    }
+}
+
+// colours taken this round become visible; counts the rows still uncoloured and the largest colour
+__global__ void colour_apply_kernel(int n, const int* newc, int* colour, unsigned long long* left, int* cmax) {
+    const int i = blockIdx.x * kT + threadIdx.x;
+    if (i >= n) return;
+    if (newc[i] >= 0) {
+        colour[i] = newc[i];
+        atomicMax(cmax, newc[i]);
+    } else if (colour[i] < 0) {
+        atomicAdd(left, 1ull);
+    }
+}
+
 // halo forwarding: packed[t] = local[send_idx[t]]
 template <class T>
 __global__ void pack_kernel_t(int n, const int* idx, const T* local, T* packed) {
@@ -1678,6 +1744,62 @@ void pmis_split(LevelCtx& L, const DCsr& Sv, DevBuf<int>& cf) {
     }
 }
 
+// the multicolour ordering of A's rows: pmis_split's stages on the operator's own
+// pattern -- the local transpose adjacency, the off-rank dependents and their halo, synchronous
+// rounds with one scalar back per round.  Collective on a distributed level
+void colour_rows(LevelCtx& L, Colouring& out) {
+    hipStream_t s = L.s;
+    const HostComm& comm = L.comm;
+    const int n = L.n, lo = L.lo;
+    const bool dist = L.dist;
+    const DCsr& Av = L.Av;
+    DevBuf<int> tcnt, trp, tcol, cursor;
+    tcnt.alloc((size_t)n + 1);
+    HIP_CHECK(hipMemsetAsync(tcnt.p, 0, sizeof(int) * tcnt.n, s));
+    launch_rows(s, n, col_count_kernel, Av, tcnt.p);
+    trp.alloc((size_t)n + 1);
+    const int64_t tnnz = exclusive_scan(s, tcnt.p, trp.p, n, L.tmp);
+    tcol.alloc((size_t)std::max<int64_t>(tnnz, 1));
+    cursor.alloc((size_t)n + 1);
+    HIP_CHECK(hipMemcpyAsync(cursor.p, trp.p, sizeof(int) * (n + 1), hipMemcpyDeviceToDevice, s));
+    launch_rows(s, n, transpose_fill_kernel, Av, cursor.p, tcol.p);
+    DevBuf<int> erp, ecol;
+    DevHalo H;
+    H.build(dist ? offrank_dependents(L, Av, erp, ecol) : HaloPlan());
+    const Dist Dn = H.dist(lo, n);
+    DevBuf<unsigned> key, hkey;
+    DevBuf<int> colour, hcolour, newc, cmax;
+    DevBuf<unsigned long long> left;
+    key.alloc((size_t)std::max(n, 1));
+    colour.alloc((size_t)std::max(n, 1));
+    newc.alloc((size_t)std::max(n, 1));
+    hkey.alloc(1);
+    hcolour.alloc(1);
+    left.alloc(1);
+    cmax.alloc(1);
+    HIP_CHECK(hipMemsetAsync(cmax.p, 0xFF, sizeof(int), s));  // -1: no colour yet
+    launch_rows(s, n, colour_init_kernel, n, lo, (unsigned long long)L.seed(), key.p, colour.p);
+    if (dist) H.forward(s, comm, key.p, hkey);
+    int64_t rows_left = dist ? comm.allreduce_sum(n) : n;
+    int round = 0;
+    for (; rows_left > 0; ++round) {
+        AMG_CHECK(round <= L.A.n_global_rows, "multicolour ordering did not terminate");
+        if (dist) H.forward(s, comm, colour.p, hcolour);
+        launch_rows(s, n, colour_select_kernel, Av, Dn, trp.p, tcol.p, dist ? erp.p : nullptr,
+                    dist ? ecol.p : nullptr, key.p, hkey.p, colour.p, hcolour.p, newc.p);
+        HIP_CHECK(hipMemsetAsync(left.p, 0, sizeof(unsigned long long), s));
+        launch_rows(s, n, colour_apply_kernel, n, newc.p, colour.p, left.p, cmax.p);
+        const int64_t l = (int64_t)read_scalar(s, left.p);
+        rows_left = dist ? comm.allreduce_sum(l) : l;
+    }
+    int64_t nc = (int64_t)read_scalar(s, cmax.p) + 1;
+    if (dist)
+        for (int64_t v : comm.allgather(nc)) nc = std::max(nc, v);
+    out.colour = download_ints(s, colour.p, n);
+    out.n_colours = (int32_t)nc;
+    out.rounds = round;
+}
+
 // coarse numbering: C points in row order, ranks in order
 struct CoarseIds : Pinned {
     std::vector<int64_t> cstarts;  // the coarse partition
@@ -2122,6 +2244,28 @@ bool level_setup_device(Context& ctx, const HostComm& comm, const HostCSR& A, co
     if (opt.coarsen == AMG_COARSEN_PMIS) return pmis_level(L, P, split, im, ext_stats);
     AMG_CHECK(opt.coarsen == AMG_COARSEN_SA, "unknown coarsening");
     return sa_level(L, P, split, im);
+}
+
+// The multicolour ordering of A's rows with the hash keys of `seed` (a solver's level l:
+// opt.seed + l).  imgs: A's device image where a setup holds it; otherwise A is uploaded for
+// the call.  Collective over the ranks of comm.
+Colouring colour_device(Context& ctx, const HostComm& comm, const HostCSR& A, uint64_t seed, SetupImages* imgs) {
+    Colouring out;
+    AMG_CHECK(A.n_global_rows == A.n_global_cols && A.row_starts == A.col_starts,
+              "multicolour ordering needs a square matrix");
+    if (comm.nranks == 1 && A.nrows() == 0) return out;
+    AMG_CHECK(A.nrows() < INT_MAX && A.n_global_cols < INT_MAX, "multicolour ordering: level exceeds int32 indexing");
+    amg_options opt{};
+    opt.seed = seed;
+    LevelCtx L(ctx.stream, comm, A, opt, 0);
+    SetupImages local;
+    SetupImages& im = imgs && imgs->find(A) ? *imgs : local;
+    DevCsr& DA = im.get(A);
+    DA.ensure_rp32(L.s);
+    DA.ensure_col32(L.s);
+    L.Av = DCsr{DA.rp32.p, DA.col32.p, DA.val.p, L.n, L.lo};
+    colour_rows(L, out);
+    return out;
 }
 
 namespace {
