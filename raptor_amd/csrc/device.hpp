@@ -742,15 +742,33 @@ struct Solver {
     bool graph_ready(int slot, const double* x, const double* b, const std::function<void()>& body,
                      bool agree);
     void agree_stale(std::initializer_list<int> slots, const double* x, const double* b);
+    // `body` run under a thread-local stream capture with ctx->capturing set (reset whatever
+    // the body does): the captured graph (the caller's to destroy; null where the runtime
+    // gave none), the body's error text and amg::Error code, the end-capture status
+    struct Captured {
+        hipGraph_t graph = nullptr;
+        std::string err;
+        int err_code = AMG_ERR_INTERNAL;
+        hipError_t end = hipSuccess;
+    };
+    Captured capture(const std::function<void()>& body);
+    // replay slot's graph for (x, b) where graphs are on and it is ready, else run body eagerly
+    // (inside the roctx range eager_range, where given)
+    void run(int slot, const double* x, const double* b, const std::function<void()>& body, bool agree = false,
+             const char* eager_range = nullptr);
     void graph_launch(int slot);
     void destroy_graphs();
     void drop_graph(Graph& G);  // destroy one exec once the stream has drained
 
     DevMatrix& Amat(size_t l) { return l == 0 ? *A0 : *levels[l].A; }
+    const DevMatrix& Amat(size_t l) const { return l == 0 ? *A0 : *levels[l].A; }
     // the operators the cycle runs (cycle-order copies where they exist)
     DevMatrix& CA(size_t l) { return l > 0 && levels[l].Ac ? *levels[l].Ac : Amat(l); }
     DevMatrix& CP(size_t l) { return levels[l].Pc ? *levels[l].Pc : *levels[l].P; }
     DevMatrix& CR(size_t l) { return levels[l].Rc ? *levels[l].Rc : *levels[l].R; }
+    const DevMatrix& CA(size_t l) const { return l > 0 && levels[l].Ac ? *levels[l].Ac : Amat(l); }
+    const DevMatrix& CP(size_t l) const { return levels[l].Pc ? *levels[l].Pc : *levels[l].P; }
+    const DevMatrix& CR(size_t l) const { return levels[l].Rc ? *levels[l].Rc : *levels[l].R; }
     void setup(DevMatrix& A, const amg_options& o);
     // one V-cycle; with_norm: the first level-0 Jacobi sweep also appends ||b - A x_in||
     // to the device history (falls back to a separate residual when it cannot).  agree: the
@@ -761,9 +779,22 @@ struct Solver {
     // x0_in_t: level l's first pre-sweep from x = 0 already sits in levels[l].t (fused into
     // the restriction above, par_restrict_j0)
     void cycle_rec(size_t l, double* x, const double* b, bool x_zero, bool with_norm, bool x0_in_t = false);
-    // x0_in_t (Chebyshev): step 0 of this application already sits in tmp
-    void smooth(size_t l, double*& x, const double* b, double*& tmp, bool x_zero, bool with_norm,
-                bool post = false, bool x0_in_t = false);
+    // one smoothing application of level l: x and tmp swap roles where the sweep writes tmp
+    struct Sweep {
+        bool from_zero = false;  // x is zero (not yet written)
+        bool with_norm = false;  // also appends ||b - A x_in|| to the device history
+        bool post = false;       // after the coarse correction
+        bool x0_in_t = false;    // the first step from zero already sits in tmp (par_restrict_j0)
+    };
+    void smooth(size_t l, double*& x, const double* b, double*& tmp, const Sweep& w);
+    void smooth_jacobi(size_t l, double*& x, const double* b, double*& tmp, const Sweep& w);
+    void smooth_cheby(size_t l, double*& x, const double* b, double*& tmp, const Sweep& w);
+    void smooth_hybrid_gs(size_t l, double*& x, const double* b, double*& tmp, const Sweep& w);
+    void smooth_mc_gs(size_t l, double* x, const double* b, const Sweep& w);
+    // every rank's `slot` (cmax doubles behind pad's nranks x cmax gather area) allgathered
+    // into pad, then each rank's starts[q + 1] - starts[q] values copied to dst + starts[q]
+    void allgather_unpad(const double* slot, double* pad, int64_t cmax, const std::vector<int64_t>& starts,
+                         double* dst);
     // Chebyshev smoother: per non-coarsest level the estimate lambda_l of
     // rho(D^-1 A_l) and the coefficients of the degree-m polynomial on [f hi, hi], hi = 1.1 lambda_l
     // (c1[k], c2[k] for step k >= 1; entry 0 unused).  Launch arguments of the cycle's kernels
@@ -781,6 +812,14 @@ struct Solver {
     // operator passes of one smoothing application (Chebyshev: its degree)
     int sweep_steps() const { return opt.smoother == AMG_SMOOTH_CHEBYSHEV ? opt.cheby_degree : 1; }
     void ensure_hist(int32_t n);
+    // the frame of solve / pcg / bicgstab: room for max_iter + 1 norms, earlier calls' replays
+    // fenced (N ranks), the history counter zeroed
+    void begin_history(int32_t max_iter);
+    double read_scalar(const double* dev);                // to the host, stream synchronised
+    void download_history(double* hist_host, size_t n);  // the first n norms, synchronised
+    // a and b grown to na and nb doubles; the graphs in `slots` (which baked their addresses)
+    // are dropped first if either grows.  True where b grew
+    bool grow_work(DevBuf<double>& a, size_t na, DevBuf<double>& b, size_t nb, std::initializer_list<int> slots);
     bool can_fuse_norm() const;
     // ParMultilevel::solve; hist_host gets it+1 norms
     int32_t solve(double* x, const double* b, int32_t max_iter, double tol, double* hist_host);

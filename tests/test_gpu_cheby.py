@@ -1,6 +1,6 @@
-"""The Chebyshev smoother on the GPU (KM_CHEBY in kernels.hip, Solver::setup_cheby / smooth in
-multilevel.hip) against the restatement of tests/cheby_cases.py (checked on the CPU by
-tests/test_cheby_cpu.py), exact int64 arithmetic, exact fixed points and poisoned columns.
+"""The Chebyshev smoother on the GPU (KM_CHEBY in kernels.hip, Solver::setup_cheby in
+solver_setup.hip, Solver::smooth in multilevel.hip) against the restatement of
+tests/cheby_cases.py (checked on the CPU by tests/test_cheby_cpu.py), exact int64 arithmetic, exact fixed points and poisoned columns.
 
 Bars: chebyshev_step, level_eig, V-cycle, solve and PCG iterates bit-identical (edge_cases.bits);
 solve histories within 1e-10 relative, entries left by a fused norm within 1e-12; PCG history

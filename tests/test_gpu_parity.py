@@ -4,6 +4,9 @@ Bar: bit-identical for every kernel and every V-cycle iterate (bot
 round each product and sum as written, same order); residual norms (different reduction
 order) within 1e-12 relative; solve histories within 1e-10 relative (BASELINE.json:5).
 Parity against Siddarthareddy1/raptor itself is unpinned (no AMG code in the reference)."""
+import json
+import os
+
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -425,6 +428,32 @@ def test_cycle_timeline(ctx, oracle, coarsen, smoother):
     for _ in range(5):
         ml.cycle(x2, b)
     assert np.array_equal(to_host(ctx, x), to_host(ctx, x2))
+
+
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+with open(os.path.join(_GOLDEN, "cycle_labels.json")) as _f:
+    CYCLE_LABELS = json.load(_f)  # recorded by tests/golden/gen_cycle_labels.py
+
+
+@pytest.mark.parametrize("case", CYCLE_LABELS,
+                         ids=lambda c: "-".join(str(v) for v in c["options"].values()))
+def test_cycle_operation_order(ctx, oracle, case):
+    """The operations of one V-cycle, in order (the labels of amg_solver_cycle_timeline without
+    the trailing "event-node gap"), equal the recorded list for every smoother and sweep option
+    of tests/golden/cycle_labels.json, replayed from a captured graph and launched eagerly."""
+    import raptor_amd as ra
+
+    A = ra.par_stencil_grid(ctx, "7pt", (28, 26, 24))
+    n = A.local_rows
+    b = to_dev(ctx, oracle.vec_uniform(n, 42))
+    ml = ra.ParMultilevel(**case["options"]).setup(A)
+    for graph in (True, False):
+        ml.set_graph(graph)
+        ops, mode = ml.cycle_timeline(ctx.zeros(n), b, reps=1)
+        assert (mode >= 1) == graph
+        labels = [lab for lab, _ in ops if lab != "event-node gap"]
+        print(graph, labels)
+        assert labels == case["labels"], (graph, labels)
 
 
 CASES = [
