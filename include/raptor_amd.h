@@ -83,6 +83,23 @@ int amg_context_destroy(amg_context ctx);
 int amg_par_csr_create(amg_context ctx, int64_t n_global, int64_t first_row, int64_t n_local,
                        const int64_t* row_ptr, const int64_t* col_global, const double* val,
                        amg_matrix* out);
+/* A rectangular operator (an interpolation or a restriction on its own): rank-local rows
+ * [first_row, first_row + n_local_rows) of an n_global_rows x n_global_cols matrix whose
+ * columns are partitioned independently of its rows -- this rank owns the columns
+ * [first_col, first_col + n_local_cols), the part of x it passes to amg_par_csr_mult.  Both
+ * ranges must follow the rank order and tile [0, n_global_rows) / [0, n_global_cols); the
+ * arrays are validated like amg_par_csr_create's (columns in [0, n_global_cols), unsorted
+ * rows sorted, duplicate columns rejected).  Collective.
+ * The handle takes amg_par_csr_mult, _mult_add, _export, _info, _set_format and
+ * _format_digest.  Every call that needs a diagonal or a solver (residual, jacobi,
+ * chebyshev_step, the GS sweeps, residual_norm, colour, mc_gs, reorder, amg_solver_setup)
+ * returns AMG_ERR_INVALID before any device work unless the operator is square with equal
+ * row and column partitions.  No setup image is kept.                                       */
+int amg_par_csr_create_rect(amg_context ctx, int64_t n_global_rows, int64_t n_global_cols,
+                            int64_t first_row, int64_t n_local_rows,
+                            int64_t first_col, int64_t n_local_cols,
+                            const int64_t* row_ptr, const int64_t* col_global, const double* val,
+                            amg_matrix* out);
 
 #define AMG_STENCIL_5PT 0    /* 2D Poisson, nz must be 1            (BASELINE.json:7)  */
 #define AMG_STENCIL_7PT 1    /* 3D Poisson                           (BASELINE.json:8)  */

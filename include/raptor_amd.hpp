@@ -85,6 +85,16 @@ public:
                  const int64_t* col_global, const double* val) {
         check(amg_par_csr_create(ctx.handle(), n_global, first_row, n_local, row_ptr, col_global, val, &h_));
     }
+    // a rectangular operator (an interpolation or restriction on its own): rows and columns
+    // partitioned independently; mult, mult_add, info and set_format only.  Collective.
+    static ParCSRMatrix rect(Context& ctx, int64_t n_global_rows, int64_t n_global_cols, int64_t first_row,
+                             int64_t n_local_rows, int64_t first_col, int64_t n_local_cols,
+                             const int64_t* row_ptr, const int64_t* col_global, const double* val) {
+        amg_matrix h = nullptr;
+        check(amg_par_csr_create_rect(ctx.handle(), n_global_rows, n_global_cols, first_row, n_local_rows,
+                                      first_col, n_local_cols, row_ptr, col_global, val, &h));
+        return ParCSRMatrix(h, true);
+    }
     // this rank's slab of a model problem (AMG_STENCIL_5PT / 7PT / 27PT).  Collective.
     static ParCSRMatrix stencil(Context& ctx, int kind, int64_t nx, int64_t ny, int64_t nz,
                                 const double* eps3 = nullptr) {

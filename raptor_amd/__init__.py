@@ -363,6 +363,27 @@ class ParCSRMatrix:
         return cls(ctx, h)
 
     @classmethod
+    def from_csr_rect(cls, ctx: Context, shape, first_row: int, first_col: int, n_local_cols: int,
+                      row_ptr, col, val):
+        """A rectangular operator of global ``shape`` = (rows, columns): this rank's rows from
+        ``first_row`` (``row_ptr.size - 1`` of them) and its own columns ``[first_col, first_col +
+        n_local_cols)``, the part of x it passes to ``mult``.  The two partitions are independent.
+        The handle takes mult, mult_add, export, info, set_format and format_digest; every other
+        call raises AmgError.  Collective."""
+        rp = np.ascontiguousarray(row_ptr, np.int64)
+        cg = np.ascontiguousarray(col, np.int64)
+        v = np.ascontiguousarray(val, np.float64)
+        if rp.ndim != 1 or rp.size < 1 or cg.size != rp[-1] or v.size != rp[-1]:
+            raise ValueError("row_ptr / col / val sizes are inconsistent")
+        h = C.c_void_p()
+        i64 = C.POINTER(C.c_int64)
+        check(lib().amg_par_csr_create_rect(ctx.h, int(shape[0]), int(shape[1]), int(first_row), rp.size - 1,
+                                            int(first_col), int(n_local_cols), rp.ctypes.data_as(i64),
+                                            cg.ctypes.data_as(i64), v.ctypes.data_as(C.POINTER(C.c_double)),
+                                            C.byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
     def from_scipy_local(cls, ctx: Context, M, n_global: int, first_row: int):
         M = M.tocsr()
         return cls.from_csr(ctx, n_global, first_row, M.indptr, M.indices, M.data)

@@ -123,6 +123,8 @@ SIGNATURES = {
     "amg_context_synchronize": (C.c_int, [_vp]),
     "amg_context_destroy": (C.c_int, [_vp]),
     "amg_par_csr_create": (C.c_int, [_vp, _i64, _i64, _i64, _pi64, _pi64, _pf64, C.POINTER(_vp)]),
+    "amg_par_csr_create_rect": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _pi64, _pi64, _pf64,
+                                          C.POINTER(_vp)]),
     "amg_par_stencil_create": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, _pf64, C.POINTER(_vp)]),
     "amg_par_stencil_create_boxes": (C.c_int, [_vp, C.c_int, _i64, _i64, _i64, _i64, _i64, _i64, _pf64,
                                                C.POINTER(_vp)]),

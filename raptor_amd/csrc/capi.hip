@@ -49,19 +49,39 @@ static int guard(F&& f) {
 
 static void set_device(Context& c) { HIP_CHECK(hipSetDevice(c.device)); }
 
-static HostCSR make_host_csr(const HostComm& comm, int64_t n_global, int64_t first_row,
-                             int64_t n_local, const int64_t* row_ptr, const int64_t* col_global,
-                             const double* val) {
+// The calls that need the diagonal or a row-to-column correspondence refuse a rectangular
+// operator first: before the vector checks, the halo exchange and any launch.
+static void need_square(const DevMatrix& M, const char* call) {
+    AMG_CHECK(M.square, std::string(call) + ": needs a square matrix (rows and columns partitioned alike)");
+}
+
+// The caller's rows as a HostCSR: both partitions allgathered and checked against the rank
+// order, row pointers and column ids validated, unsorted rows sorted, duplicate columns
+// rejected.  A square operator (amg_par_csr_create) passes its row partition twice.
+static HostCSR make_host_csr(const HostComm& comm, int64_t n_global_rows, int64_t n_global_cols,
+                             int64_t first_row, int64_t n_local, int64_t first_col, int64_t n_local_cols,
+                             const int64_t* row_ptr, const int64_t* col_global, const double* val) {
     AMG_CHECK(row_ptr, "null row_ptr");
-    AMG_CHECK(n_local >= 0 && first_row >= 0 && first_row + n_local <= n_global, "bad row range");
+    AMG_CHECK(n_local >= 0 && first_row >= 0 && first_row + n_local <= n_global_rows, "bad row range");
+    AMG_CHECK(n_local_cols >= 0 && first_col >= 0 && first_col + n_local_cols <= n_global_cols,
+              "bad column range");
     HostCSR h;
-    h.n_global_rows = h.n_global_cols = n_global;
-    std::vector<int64_t> counts = comm.allgather(n_local);
-    h.row_starts.assign(comm.nranks + 1, 0);
-    for (int r = 0; r < comm.nranks; ++r) h.row_starts[r + 1] = h.row_starts[r] + counts[r];
+    h.n_global_rows = n_global_rows;
+    h.n_global_cols = n_global_cols;
+    auto starts = [&](int64_t n_mine) {
+        const std::vector<int64_t> counts = comm.allgather(n_mine);
+        std::vector<int64_t> st((size_t)comm.nranks + 1, 0);
+        for (int r = 0; r < comm.nranks; ++r) st[r + 1] = st[r] + counts[r];
+        return st;
+    };
+    // both allgathers before either check: a rank that throws must not leave the others waiting
+    h.row_starts = starts(n_local);
+    h.col_starts = starts(n_local_cols);
     AMG_CHECK(h.row_starts[comm.rank] == first_row, "first_row inconsistent with rank order");
-    AMG_CHECK(h.row_starts[comm.nranks] == n_global, "local row counts do not sum to n_global");
-    h.col_starts = h.row_starts;
+    AMG_CHECK(h.row_starts[comm.nranks] == n_global_rows, "local row counts do not sum to n_global");
+    AMG_CHECK(h.col_starts[comm.rank] == first_col, "first_col inconsistent with rank order");
+    AMG_CHECK(h.col_starts[comm.nranks] == n_global_cols, "local column counts do not sum to n_global_cols");
+    const int64_t n_global = n_global_cols;  // the range of a column id
     AMG_CHECK(row_ptr[0] == 0, "row_ptr[0] must be 0");
     const int64_t nnz = row_ptr[n_local];
     h.rp.assign(row_ptr, row_ptr + n_local + 1);
@@ -232,11 +252,30 @@ int amg_par_csr_create(amg_context ctx, int64_t n_global, int64_t first_row, int
         AMG_CHECK(n_local >= 0 && first_row >= 0 && first_row + n_local <= n_global, "bad row range");
         Context& c = ctx->c;
         set_device(c);
-        HostCSR h = make_host_csr(c.host, n_global, first_row, n_local, row_ptr, col_global, val);
+        HostCSR h = make_host_csr(c.host, n_global, n_global, first_row, n_local, first_row, n_local, row_ptr,
+                                  col_global, val);
         std::unique_ptr<amg_matrix_s> m(new amg_matrix_s());
         m->own.reset(new DevMatrix());
         m->m = m->own.get();
         m->m->keep_setup_csr = true;  // the level-0 operator of a later solver setup
+        m->m->build(&c, std::move(h));
+        *out = m.release();
+    });
+}
+
+int amg_par_csr_create_rect(amg_context ctx, int64_t n_global_rows, int64_t n_global_cols, int64_t first_row,
+                            int64_t n_local_rows, int64_t first_col, int64_t n_local_cols,
+                            const int64_t* row_ptr, const int64_t* col_global, const double* val,
+                            amg_matrix* out) {
+    return guard([&] {
+        AMG_CHECK(ctx && out && row_ptr, "null argument");
+        Context& c = ctx->c;
+        set_device(c);
+        HostCSR h = make_host_csr(c.host, n_global_rows, n_global_cols, first_row, n_local_rows, first_col,
+                                  n_local_cols, row_ptr, col_global, val);
+        std::unique_ptr<amg_matrix_s> m(new amg_matrix_s());
+        m->own.reset(new DevMatrix());
+        m->m = m->own.get();  // no setup image: an interpolation or restriction is no level 0
         m->m->build(&c, std::move(h));
         *out = m.release();
     });
@@ -326,6 +365,7 @@ int amg_par_csr_reorder(amg_matrix A, int method, amg_matrix* out, int64_t* new_
     return guard([&] {
         AMG_CHECK(A && out && new_to_old_local, "null argument");
         AMG_CHECK(method == AMG_REORDER_RCM, "unknown reorder method");
+        need_square(*A->m, "reorder");
         Context& c = *A->m->ctx;
         set_device(c);
         std::vector<int64_t> n2o;
@@ -488,6 +528,7 @@ static int apply(amg_matrix A, int mode, const char* call, const char* yname, co
     return guard([&] {
         AMG_CHECK(A, "null matrix");
         const int64_t nr = A->m->n_rows, nc = A->m->n_cols_local;
+        if (mode == KM_RESID || mode == KM_JACOBI) need_square(*A->m, call);
         if (mode == KM_RESID || mode == KM_JACOBI)
             check_vectors(call, {yname, y, nr, 0}, {{"x", x, nc, kNoOverlap}, {"b", b, nr, kSameOk}});
         else
@@ -516,6 +557,7 @@ int amg_par_csr_chebyshev_step(amg_matrix A, const double* x, const double* xp, 
                                double c1, double c2) {
     return guard([&] {
         AMG_CHECK(A, "null matrix");
+        need_square(*A->m, "chebyshev_step");
         const int64_t nr = A->m->n_rows;
         check_vectors("chebyshev_step", {"x_out", xo, nr, 0},
                       {{"x", x, A->m->n_cols_local, kNoOverlap}, {"b", b, nr, kSameOk},
@@ -530,6 +572,7 @@ int amg_par_csr_chebyshev_step(amg_matrix A, const double* x, const double* xp, 
 int amg_par_csr_hybrid_gs(amg_matrix A, const double* x, const double* b, double* xo, int64_t block) {
     return guard([&] {
         AMG_CHECK(A, "null matrix");
+        need_square(*A->m, "hybrid_gs");
         check_vectors("hybrid_gs", {"x_out", xo, A->m->n_rows, 0},
                       {{"x", x, A->m->n_cols_local, kNoOverlap}, {"b", b, A->m->n_rows, kNoOverlap}});
         set_device(*A->m->ctx);
@@ -543,6 +586,7 @@ int amg_par_csr_hybrid_gs_backward(amg_matrix A, const double* x, const double* 
                                    int64_t block) {
     return guard([&] {
         AMG_CHECK(A, "null matrix");
+        need_square(*A->m, "hybrid_gs_backward");
         check_vectors("hybrid_gs_backward", {"x_out", xo, A->m->n_rows, 0},
                       {{"x", x, A->m->n_cols_local, kNoOverlap}, {"b", b, A->m->n_rows, kNoOverlap}});
         set_device(*A->m->ctx);
@@ -556,7 +600,7 @@ int amg_par_csr_colour(amg_matrix A, uint64_t seed, int32_t* n_colours) {
     return guard([&] {
         AMG_CHECK(A, "null matrix");
         DevMatrix& M = *A->m;
-        AMG_CHECK(M.square, "colour: a square matrix");
+        need_square(M, "colour");
         set_device(*M.ctx);
         HIP_CHECK(hipStreamSynchronize(M.ctx->stream));
         M.ensure_built();
@@ -588,6 +632,7 @@ int amg_par_csr_colour_rounds(amg_matrix A, int32_t* rounds) {
 int amg_par_csr_mc_gs(amg_matrix A, double* x, const double* b, int32_t backward, int32_t path) {
     return guard([&] {
         AMG_CHECK(A, "null matrix");
+        need_square(*A->m, "mc_gs");
         // x is in-out and read by other rows' lanes; b is read once per row
         check_vectors("mc_gs", {"x", x, A->m->n_cols_local, 0}, {{"b", b, A->m->n_rows, kNoOverlap}});
         set_device(*A->m->ctx);
@@ -614,6 +659,7 @@ int amg_par_csr_matmat(amg_matrix A, amg_matrix B, amg_matrix* out) {
 int amg_par_csr_residual_norm(amg_matrix A, const double* x, const double* b, double* out) {
     return guard([&] {
         AMG_CHECK(A && out, "null argument");
+        need_square(*A->m, "residual_norm");
         check_vectors("residual_norm", {nullptr, nullptr, 0, 0},
                       {{"x", x, A->m->n_cols_local, 0}, {"b", b, A->m->n_rows, 0}});
         Context& c = *A->m->ctx;
@@ -684,6 +730,7 @@ int amg_options_default(int preset, amg_options* o) {
 int amg_solver_setup(amg_matrix A, const amg_options* opt, amg_solver* out) {
     return guard([&] {
         AMG_CHECK(A && opt && out, "null argument");
+        need_square(*A->m, "solver_setup");
         set_device(*A->m->ctx);
         A->m->ensure_built();
         auto* s = new amg_solver_s();
@@ -908,7 +955,8 @@ int amg_host_hierarchy_build(int rank, int nranks, amg_alltoallv_fn exchange, vo
         h->comm.nranks = nranks;
         h->comm.fn = exchange;
         h->comm.user = user;
-        h->A0 = make_host_csr(h->comm, n_global, first_row, n_local, row_ptr, col_global, val);
+        h->A0 = make_host_csr(h->comm, n_global, n_global, first_row, n_local, first_row, n_local, row_ptr,
+                              col_global, val);
         build_hierarchy(h->comm, h->A0, *opt, h->H);
         *out = h.release();
     });
