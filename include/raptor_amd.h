@@ -386,11 +386,53 @@ int amg_solver_pcg(amg_solver S, double* x, const double* b, int32_t max_iter, d
  * quotient) and *iters the number of history entries minus one.  r = 0 at entry gives
  * *iters = 0, hist = [0], BREAKDOWN and leaves x untouched.  hist: max_iter + 1 doubles.
  * The scalars stay on the device: with tol == 0 nothing waits for the host inside the loop.
- * max_iter < 0 or overlapping x, b: AMG_ERR_INVALID before any work. */
+ * max_iter < 0 or overlapping x, b: AMG_ERR_INVALID before any work.
+ * amg_solver_fgmres (below) spends one cycle per iteration and has the happy breakdown only. */
 #define AMG_KRYLOV_OK 0
 #define AMG_KRYLOV_BREAKDOWN 1
 int amg_solver_bicgstab(amg_solver S, double* x, const double* b, int32_t max_iter, double tol,
                         double* hist, int32_t* iters, int32_t* status);
+/* Restarted flexible GMRES for nonsymmetric operators, right-preconditioned by one V-cycle per
+ * iteration (M(v): one cycle on A z = v from z = 0), one-pass classical Gram-Schmidt.  With dot
+ * the rank-ordered dot product of amg_solver_pcg, every operation rounded as written and
+ * sqrt(h h + e e) meant literally (no hypot):
+ *   k = 0; status = OK
+ *   outer:
+ *     r = b - A x; beta = sqrt(dot(r, r)); first pass only: hist[0] = beta
+ *     beta not finite: BREAKDOWN, return.  beta == 0 or k == max_iter: return
+ *     v_0 = r / beta (a division per entry); g_0 = beta; J = 0
+ *     for j = 0 .. restart-1 while k < max_iter:
+ *       z_j = M(v_j); w = A z_j
+ *       c_i = dot(v_i, w), i = 0..j                    (all from the same w)
+ *       w = ((w - c_0 v_0) - c_1 v_1) ... - c_j v_j    (per entry, i ascending)
+ *       eta = sqrt(dot(w, w)); h_i = c_i (i <= j); h_{j+1} = eta
+ *       i = 0..j-1: t = cs_i h_i + sn_i h_{i+1}; h_{i+1} = (-(sn_i h_i)) + cs_i h_{i+1}; h_i = t
+ *       d = sqrt(h_j h_j + h_{j+1} h_{j+1})
+ *       d == 0 or not finite: BREAKDOWN, leave the loop (k not counted, column j not used)
+ *       cs_j = h_j / d; sn_j = h_{j+1} / d; h_j = d
+ *       g_{j+1} = -(sn_j g_j); g_j = cs_j g_j
+ *       column j of H = h_0..h_j; J = j + 1; k = k + 1; hist[k] = |g_{j+1}|
+ *       eta == 0: stop (happy breakdown: status stays OK)
+ *       tol > 0 and hist[0] > 0 and hist[k] / hist[0] < tol: stop
+ *       v_{j+1} = w / eta (a division per entry)
+ *     y_i, i = J-1 .. 0: s = g_i; s = s - H_il y_l for l = i+1 .. J-1 ascending; y_i = s / H_ii
+ *     x = ((x + y_0 z_0) + y_1 z_1) ... + y_{J-1} z_{J-1}    (per entry, i ascending)
+ *     stop, BREAKDOWN or k == max_iter: return, else the next outer pass
+ * hist[0] is ||b - A x_0||; hist[k], k >= 1, is the Arnoldi estimate |g_{j+1}| of ||b - A x_k||,
+ * not a norm computed from x_k (it falls monotonically inside a cycle).  hist: max_iter + 1
+ * doubles; *iters = k.  The vector contract is amg_solver_bicgstab's.  A breakdown is a status:
+ * the call returns AMG_OK, *status is AMG_KRYLOV_BREAKDOWN and x holds the update over the columns
+ * completed (never a non-finite value from a failed quotient).  r = 0 at entry gives *iters = 0,
+ * hist = [0], status OK and leaves x untouched; max_iter == 0 gives hist = [beta], x untouched.
+ * j, k, the stop flag, g, cs, sn, H, c and y stay on the device: with tol == 0 nothing waits for
+ * the host between the first step and the history download.
+ * Workspace: (2 restart + 3) n doubles of device memory (n local rows), allocated on the first
+ * call and regrown when restart grows; regrowing drops the captured iteration graphs.
+ * restart outside 1 .. AMG_FGMRES_MAX_RESTART, max_iter < 0 or overlapping x, b: AMG_ERR_INVALID
+ * before any work, nothing written. */
+#define AMG_FGMRES_MAX_RESTART 64
+int amg_solver_fgmres(amg_solver S, double* x, const double* b, int32_t restart, int32_t max_iter,
+                      double tol, double* hist, int32_t* iters, int32_t* status);
 /* Capture each V-cycle in a hipGraph and replay it (1 = on).  Default: on for 1 rank; off
  * for loopback ranks (they meet at host barriers); for RCCL ranks on where the process runs
  * the runtime whole-cycle capture was validated on (HIP >= 7.2 with RCCL >= 2.27.7: the

@@ -285,6 +285,17 @@ public:
         if (status) *status = st;
         return hist;
     }
+    // restarted flexible GMRES for nonsymmetric operators, right-preconditioned by one V-cycle
+    // per iteration; the history holds ||b - A x_0||, then the Arnoldi residual estimates
+    std::vector<double> fgmres(double* x, const double* b, int max_iter, double tol = 0.0, int restart = 30,
+                               int* status = nullptr) {
+        std::vector<double> hist((size_t)(max_iter > 0 ? max_iter : 0) + 1);
+        int32_t it = 0, st = AMG_KRYLOV_OK;
+        check(amg_solver_fgmres(h_, x, b, restart, max_iter, tol, hist.data(), &it, &st));
+        hist.resize((size_t)it + 1);
+        if (status) *status = st;
+        return hist;
+    }
     amg_solver handle() const { return h_; }
 
 private:

@@ -821,6 +821,18 @@ class ParMultilevel:
                                         C.byref(st)))
         return x, hist[: it.value + 1], int(st.value)
 
+    def fgmres(self, x, b, max_iter=20, tol=0.0, restart=30):
+        """Restarted flexible GMRES for nonsymmetric operators, right-preconditioned by one
+        V-cycle per iteration (``restart`` 1 .. 64 columns per cycle; workspace ``(2 restart + 3)
+        n`` doubles).  Returns ``(x, hist, status)``: ``hist[0]`` is ``||b - A x_0||``, the later
+        entries are the Arnoldi residual estimates; ``status`` as in :meth:`bicgstab`."""
+        hist = np.zeros(max(int(max_iter), 0) + 1)
+        it, st = C.c_int32(), C.c_int32()
+        check(lib().amg_solver_fgmres(self.h, _ptr(x), _ptr(b), int(restart), int(max_iter), float(tol),
+                                      hist.ctypes.data_as(C.POINTER(C.c_double)), C.byref(it),
+                                      C.byref(st)))
+        return x, hist[: it.value + 1], int(st.value)
+
     def _release(self):
         h = getattr(self, "h", None)
         self.h = None

@@ -167,6 +167,8 @@ SIGNATURES = {
     "amg_solver_pcg": (C.c_int, [_vp, _vp, _vp, _i32, _f64, _pf64, C.POINTER(_i32)]),
     "amg_solver_bicgstab": (C.c_int, [_vp, _vp, _vp, _i32, _f64, _pf64, C.POINTER(_i32),
                                       C.POINTER(_i32)]),
+    "amg_solver_fgmres": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _f64, _pf64, C.POINTER(_i32),
+                                    C.POINTER(_i32)]),
     "amg_solver_set_graph": (C.c_int, [_vp, _i32]),
     "amg_solver_get_graph": (C.c_int, [_vp, C.POINTER(_i32)]),
     "amg_solver_cycle_timeline": (C.c_int, [_vp, _vp, _vp, _i32, _i32, C.POINTER(C.c_double), C.c_char_p, _i32,

@@ -886,6 +886,18 @@ int amg_solver_bicgstab(amg_solver S, double* x, const double* b, int32_t max_it
     });
 }
 
+int amg_solver_fgmres(amg_solver S, double* x, const double* b, int32_t restart, int32_t max_iter,
+                      double tol, double* hist, int32_t* iters, int32_t* status) {
+    return guard([&] {
+        AMG_CHECK(S && hist && iters && status, "null argument");
+        AMG_CHECK(restart >= 1 && restart <= AMG_FGMRES_MAX_RESTART, "restart must be 1 .. AMG_FGMRES_MAX_RESTART");
+        AMG_CHECK(max_iter >= 0, "max_iter must be >= 0");
+        check_solver_vectors("fgmres", S, x, b);
+        set_device(*S->s.ctx);
+        *iters = S->s.fgmres(x, b, restart, max_iter, tol, hist, status);
+    });
+}
+
 int amg_solver_set_graph(amg_solver S, int32_t enable) {
     return guard([&] {
         AMG_CHECK(S, "null solver");

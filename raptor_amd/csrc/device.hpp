@@ -630,6 +630,51 @@ void launch_bicg_tsdot(hipStream_t s, int64_t n, const double* sc, const double*
 void launch_bicg_xr(hipStream_t s, int64_t n, const double* sc, const double* ph, const double* sh,
                     const double* sv, const double* t, const double* rhat, double* x, double* r,
                     double* part_rr, double* part_rhr);
+// FGMRES helpers (Solver::fgmres).  sc: the device state block -- the stop flag, the
+// column index j of the running cycle (= the columns completed, J), restart, max_iter, h0, tol,
+// the divisor of the next scale (beta or eta), g, cs, sn, the working column c / h, y and the
+// packed upper triangle H (column l at l (l + 1) / 2).  Integers are kept as doubles.  A set flag
+// makes every kernel of a step return at once; the y and x kernels run whatever the flag says
+// and apply the J columns the cycle completed.
+constexpr int kFgMax = AMG_FGMRES_MAX_RESTART;
+enum {
+    FG_FLAG = 0, FG_J, FG_M, FG_MAXIT, FG_H0, FG_TOL, FG_SCALE,
+    FG_G,                                  // kFgMax + 1
+    FG_CS = FG_G + kFgMax + 1,             // kFgMax
+    FG_SN = FG_CS + kFgMax,                // kFgMax
+    FG_C = FG_SN + kFgMax,                 // kFgMax + 1: c_0 .. c_j, then h_0 .. h_{j+1}
+    FG_Y = FG_C + kFgMax + 1,              // kFgMax
+    FG_H = FG_Y + kFgMax,                  // kFgMax (kFgMax + 1) / 2
+    FG_N = FG_H + kFgMax * (kFgMax + 1) / 2
+};
+constexpr double FG_RUN = 0.0, FG_BREAKDOWN = 1.0, FG_STOPPED = 2.0;
+// a call's start: flag cleared, j = 0, restart, max_iter and tol stored
+void launch_fgmres_init(hipStream_t s, double* sc, double tol, int restart, int max_iter);
+// Z_j = z (j read from sc)
+void launch_fgmres_keep(hipStream_t s, int64_t n, const double* sc, const double* z, double* Z, int64_t stride);
+// part[i * g + block], i = 0 .. j: dot_partials_kernel's partials of v_i . w, w read once
+void launch_fgmres_dots(hipStream_t s, int64_t n, const double* sc, const double* w, const double* V,
+                        int64_t stride, double* part);
+// out[i] = the deterministic sum of part[i * g .. + g), i = 0 .. j: launch_reduce_partials' stages
+// for every i at once (tmp: >= kFgMax * (g / 4096 + 1) doubles)
+void launch_fgmres_reduce(hipStream_t s, int g, const double* sc, const double* part, double* tmp, double* out);
+// c_i = the rank-ordered sum of in[rank * kFgMax + i], i = 0 .. j
+void launch_fgmres_c(hipStream_t s, int nr, const double* in, double* sc);
+// w = ((w - c_0 v_0) - c_1 v_1) ... - c_j v_j and dot_partials_kernel's partials of w . w
+void launch_fgmres_update(hipStream_t s, int64_t n, const double* sc, const double* V, int64_t stride,
+                          double* w, double* part);
+// eta from the rank sums of w . w; the rotations, the stopping rules, hist, j = j + 1
+void launch_fgmres_column(hipStream_t s, int nr, const double* in, double* sc, double* hist, int* counter);
+// v_j = w / sc[FG_SCALE], to the basis slot j and to vin (nothing where j == restart)
+void launch_fgmres_scale(hipStream_t s, int64_t n, const double* sc, const double* w, double* V,
+                         int64_t stride, double* vin);
+// y = the back substitution over the J completed columns
+void launch_fgmres_y(hipStream_t s, double* sc);
+// x = ((x + y_0 z_0) + y_1 z_1) ... + y_{J-1} z_{J-1}
+void launch_fgmres_x(hipStream_t s, int64_t n, const double* sc, const double* Z, int64_t stride, double* x);
+// a cycle's start: j = 0; beta from the rank sums of r . r; hist[0] on the first pass; the
+// entry rules (beta not finite, beta == 0, the iteration limit); g_0 = beta
+void launch_fgmres_begin(hipStream_t s, int nr, const double* in, double* sc, double* hist, int* counter);
 // x_i = inv_i . b, one wavefront per row, lane-interleaved partial sums + xor butterfly
 void launch_dense_gemv(hipStream_t s, int64_t n_local, int64_t n, const double* inv,
                        const double* b, double* x);
@@ -730,11 +775,12 @@ struct Solver {
         const double* x = nullptr;
         const double* b = nullptr;
         int64_t fmt_gen = -1;
-    } graphs[7];  // [0] plain cycle, [1] cycle that also appends ||b - A x_in||, [2] the
+    } graphs[9];  // [0] plain cycle, [1] cycle that also appends ||b - A x_in||, [2] the
                   // residual norm alone (solve's last norm), [3] / [4] the two halves of a
-                  // PCG iteration (Solver::pcg), [5] / [6] those of a BiCGStab iteration
+                  // PCG iteration (Solver::pcg), [5] / [6] those of a BiCGStab iteration,
+                  // [7] an Arnoldi step of FGMRES, [8] its x update and restart
     enum { G_CYCLE = 0, G_CYCLE_NORM = 1, G_NORM = 2, G_PCG_STEP = 3, G_PCG_PREC = 4,
-           G_BICG_S = 5, G_BICG_XR = 6 };
+           G_BICG_S = 5, G_BICG_XR = 6, G_FGMRES_STEP = 7, G_FGMRES_RESTART = 8 };
     // the graph in `slot` captured for (x, b) -- recaptured by `body` when stale.  Multi-rank
     // with `agree`: the ranks decide together (host allgather of the stale flags, then of the
     // capture / instantiate status), so no rank captures while a peer replays.  false: the
@@ -833,6 +879,14 @@ struct Solver {
                      int32_t* status);
     // r | rhat | p | v | s | t | phat | shat ; two partial arrays | tmp | gathered | local | scalars
     DevBuf<double> bicg_vec, bicg_scratch;
+    // V-cycle-preconditioned restarted flexible GMRES (right preconditioning, one-pass classical
+    // Gram-Schmidt); hist_host gets the Arnoldi residual estimates
+    int32_t fgmres(double* x, const double* b, int32_t restart, int32_t max_iter, double tol,
+                   double* hist_host, int32_t* status);
+    // w | cycle input | cycle output | v_0 z_0 v_1 z_1 ... (restart pairs) ;
+    // restart partial arrays | tmp | gathered | local | the state block
+    DevBuf<double> fgmres_vec, fgmres_scratch;
+    int32_t fgmres_room = 0;  // the largest restart so far: what the two buffers hold
     // in-graph time of every operation of a cycle (amg_solver_cycle_timeline, one rank): while
     // tl_on, cycle_rec marks the end of each operation -- a timing event when eager, the end of
     // a captured segment (one graph per operation, replayed back to back) when capturing

@@ -2431,6 +2431,251 @@ __global__ __launch_bounds__(kTPB) void bicg_xr_kernel(long long n, const double
     dot_block_tree2(a, c, red, part_rr, part_rhr);
 }
 
+// ---- FGMRES kernels -------------------------------------------------------------
+// The state of the iteration lives in one device block sc[FG_*] (device.hpp): the column index j
+// is read there, so one launch sequence (one captured graph) serves every Arnoldi step.  Basis
+// vector i is B + i stride.  The three streaming kernels keep dot_partials_kernel's layout: block
+// g covers [g kDotSpan, (g+1) kDotSpan), lane t holds entries t + 256 k, k = 0 .. 7, in registers
+// and streams the basis against them kFgBatch vectors at a time (their loads in flight together).
+constexpr int kFgBatch = 4;
+
+__device__ __forceinline__ void fg_load8(long long n, long long base, const double* p, bool on,
+                                         double (&v)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const long long i = base + (long long)k * kTPB;
+        v[k] = on && i < n ? p[i] : 0.0;
+    }
+}
+
+// acc = (acc -+ coef_0 b_0) -+ coef_1 b_1 ... over `count` vectors, i ascending, per entry
+template <bool kAdd>
+__device__ __forceinline__ void fg_stream(long long n, long long base, int count, const double* coef,
+                                          const double* B, long long stride, double (&acc)[8]) {
+    for (int i0 = 0; i0 < count; i0 += kFgBatch) {
+        double bv[kFgBatch][8];
+#pragma unroll
+        for (int u = 0; u < kFgBatch; ++u) fg_load8(n, base, B + (long long)(i0 + u) * stride, i0 + u < count, bv[u]);
+#pragma unroll
+        for (int u = 0; u < kFgBatch; ++u) {
+            if (i0 + u >= count) break;  // grid-uniform
+            const double c = coef[i0 + u];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc[k] = kAdd ? acc[k] + c * bv[u][k] : acc[k] - c * bv[u][k];
+        }
+    }
+}
+
+// dot_partials_kernel's partials of v_i . w for i = 0 .. j in one pass: w is read once and each
+// v_i once; part[i g + block] is bit for bit what dot_partials_kernel writes for (v_i, w)
+__global__ __launch_bounds__(kTPB) void fgmres_dots_kernel(long long n, const double* sc, const double* w,
+                                                           const double* V, long long stride, double* part) {
+    __shared__ double red[2][kFgBatch][kTPB / 64];
+    if (sc[FG_FLAG] != FG_RUN) return;  // grid-uniform
+    const int count = (int)sc[FG_J] + 1;
+    const long long base = (long long)blockIdx.x * kDotSpan + threadIdx.x;
+    double wv[8];
+    fg_load8(n, base, w, true, wv);
+    int par = 0;
+    for (int i0 = 0; i0 < count; i0 += kFgBatch, par ^= 1) {
+        double bv[kFgBatch][8];
+#pragma unroll
+        for (int u = 0; u < kFgBatch; ++u) fg_load8(n, base, V + (long long)(i0 + u) * stride, i0 + u < count, bv[u]);
+        double s[kFgBatch];
+#pragma unroll
+        for (int u = 0; u < kFgBatch; ++u) {
+            s[u] = 0.0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (base + (long long)k * kTPB < n) s[u] += bv[u][k] * wv[k];
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+            for (int u = 0; u < kFgBatch; ++u) s[u] += __shfl_down(s[u], off, 64);
+        }
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int u = 0; u < kFgBatch; ++u) red[par][u][threadIdx.x >> 6] = s[u];
+        }
+        // one barrier per batch: red alternates, and the readers of batch b are past the barrier
+        // of batch b + 1 before anyone writes batch b + 2
+        __syncthreads();
+        const int u = threadIdx.x;
+        if (u < kFgBatch && i0 + u < count)
+            part[(size_t)(i0 + u) * gridDim.x + blockIdx.x] = (red[par][u][0] + red[par][u][1]) + (red[par][u][2] + red[par][u][3]);
+    }
+}
+
+// launch_reduce_partials' stage for the dot products i = 0 .. j at once: blockIdx.y = i sums
+// in[i in_stride + ...) exactly as sum_partials_kernel does
+__global__ __launch_bounds__(kTPB) void fgmres_sum_partials_kernel(int n, const double* sc, const double* in,
+                                                                   long long in_stride, double* out) {
+    __shared__ double red[kTPB / 64];
+    if (sc[FG_FLAG] != FG_RUN || (int)blockIdx.y > (int)sc[FG_J]) return;  // block-uniform
+    const double s = block_sum_span(n, in + blockIdx.y * in_stride, blockIdx.x, red);
+    if (threadIdx.x == 0) out[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+// w = ((w - c_0 v_0) - c_1 v_1) ... - c_j v_j from registers, and dot_partials_kernel's partials
+// of w . w from the values just written
+__global__ __launch_bounds__(kTPB) void fgmres_update_kernel(long long n, const double* sc, const double* V,
+                                                             long long stride, double* w, double* part) {
+    __shared__ double red[kTPB / 64];
+    if (sc[FG_FLAG] != FG_RUN) return;  // grid-uniform
+    const long long base = (long long)blockIdx.x * kDotSpan + threadIdx.x;
+    double wv[8];
+    fg_load8(n, base, w, true, wv);
+    fg_stream<false>(n, base, (int)sc[FG_J] + 1, sc + FG_C, V, stride, wv);
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const long long i = base + (long long)k * kTPB;
+        if (i < n) {
+            w[i] = wv[k];
+            s += wv[k] * wv[k];
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// x = ((x + y_0 z_0) + y_1 z_1) ... + y_{J-1} z_{J-1}: the columns the cycle completed, whatever
+// the flag says (the closing launch after a stop applies them; fgmres_begin_kernel zeroes J)
+__global__ __launch_bounds__(kTPB) void fgmres_x_kernel(long long n, const double* sc, const double* Z,
+                                                        long long stride, double* x) {
+    const int J = (int)sc[FG_J];
+    if (J == 0) return;  // grid-uniform
+    const long long base = (long long)blockIdx.x * kDotSpan + threadIdx.x;
+    double xv[8];
+    fg_load8(n, base, x, true, xv);
+    fg_stream<true>(n, base, J, sc + FG_Y, Z, stride, xv);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const long long i = base + (long long)k * kTPB;
+        if (i < n) x[i] = xv[k];
+    }
+}
+
+// v_j = w / sc[FG_SCALE] (beta or eta; a division per entry), to basis slot j and to the cycle's
+// fixed input; nothing where j == restart (the cycle is full: the restart forms v_0)
+__global__ void fgmres_scale_kernel(long long n, const double* sc, const double* w, double* V,
+                                    long long stride, double* vin) {
+    if (sc[FG_FLAG] != FG_RUN) return;
+    const int j = (int)sc[FG_J];
+    if (j >= (int)sc[FG_M]) return;
+    const double d = sc[FG_SCALE];
+    double* v = V + (long long)j * stride;
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (; i < n; i += step) {
+        const double q = w[i] / d;
+        v[i] = q;
+        vin[i] = q;
+    }
+}
+
+// Z_j = z: the cycle writes a fixed address, the basis slot depends on j
+__global__ void fgmres_keep_kernel(long long n, const double* sc, const double* z, double* Z, long long stride) {
+    if (sc[FG_FLAG] != FG_RUN || sc[FG_J] >= sc[FG_M]) return;
+    double* zj = Z + (long long)sc[FG_J] * stride;
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (; i < n; i += step) zj[i] = z[i];
+}
+
+__global__ void fgmres_init_kernel(double* sc, double tol, int restart, int max_iter) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    sc[FG_FLAG] = FG_RUN;
+    sc[FG_J] = 0.0;
+    sc[FG_M] = (double)restart;
+    sc[FG_MAXIT] = (double)max_iter;
+    sc[FG_H0] = 0.0;
+    sc[FG_TOL] = tol;
+    sc[FG_SCALE] = 0.0;
+}
+
+// c_i = v_i . w from the rank sums in[rank kFgMax + i], rank order; lane i forms c_i
+__global__ void fgmres_c_kernel(int nr, const double* in, double* sc) {
+    if (blockIdx.x != 0 || sc[FG_FLAG] != FG_RUN) return;
+    const int i = threadIdx.x;
+    if (i <= (int)sc[FG_J]) sc[FG_C + i] = rank_sum(nr, in + i, kFgMax);
+}
+
+// Column j after the update: eta = sqrt(w . w) from the rank sums; the earlier rotations applied
+// to h = (c_0 .. c_j, eta), the new rotation, g; the column stored, the iteration counted and
+// hist[k] = |g_{j+1}| appended; then the stopping rules, in the definition's order
+__global__ void fgmres_column_kernel(int nr, const double* in, double* sc, double* hist, int* counter) {
+    if (threadIdx.x != 0 || blockIdx.x != 0 || sc[FG_FLAG] != FG_RUN) return;
+    const int j = (int)sc[FG_J];
+    double* h = sc + FG_C;
+    double* cs = sc + FG_CS;
+    double* sn = sc + FG_SN;
+    double* g = sc + FG_G;
+    const double eta = sqrt(rank_sum(nr, in, 1));
+    h[j + 1] = eta;
+    for (int i = 0; i < j; ++i) {
+        const double t = cs[i] * h[i] + sn[i] * h[i + 1];
+        h[i + 1] = (-(sn[i] * h[i])) + cs[i] * h[i + 1];
+        h[i] = t;
+    }
+    const double d = sqrt(h[j] * h[j] + h[j + 1] * h[j + 1]);
+    if (d == 0.0 || !isfinite(d)) {
+        sc[FG_FLAG] = FG_BREAKDOWN;  // the iteration is not counted, column j is not used
+        return;
+    }
+    cs[j] = h[j] / d;
+    sn[j] = h[j + 1] / d;
+    h[j] = d;
+    g[j + 1] = -(sn[j] * g[j]);
+    g[j] = cs[j] * g[j];
+    double* col = sc + FG_H + j * (j + 1) / 2;
+    for (int i = 0; i <= j; ++i) col[i] = h[i];
+    sc[FG_J] = (double)(j + 1);
+    const double e = fabs(g[j + 1]);
+    hist[*counter] = e;
+    *counter += 1;
+    sc[FG_SCALE] = eta;
+    const double tol = sc[FG_TOL], h0 = sc[FG_H0];
+    if (eta == 0.0) sc[FG_FLAG] = FG_STOPPED;  // happy breakdown: the solution lies in the space
+    else if (tol > 0.0 && h0 > 0.0 && e / h0 < tol) sc[FG_FLAG] = FG_STOPPED;
+}
+
+// y_i, i = J-1 .. 0: s = g_i; s = s - H_il y_l, l ascending; y_i = s / H_ii
+__global__ void fgmres_y_kernel(double* sc) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int J = (int)sc[FG_J];
+    const double* H = sc + FG_H;
+    double* y = sc + FG_Y;
+    for (int i = J - 1; i >= 0; --i) {
+        double s = sc[FG_G + i];
+        for (int l = i + 1; l < J; ++l) s = s - H[l * (l + 1) / 2 + i] * y[l];
+        y[i] = s / H[i * (i + 1) / 2 + i];
+    }
+}
+
+// A cycle's start, after the x update and r = b - A x: J = 0 (its columns are applied); beta =
+// sqrt(r . r) from the rank sums; hist[0] = beta on a call's first pass; beta not finite is a
+// breakdown, beta == 0 or the iteration limit a stop; else g_0 = beta and v_0 = r / beta follows
+__global__ void fgmres_begin_kernel(int nr, const double* in, double* sc, double* hist, int* counter) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    sc[FG_J] = 0.0;
+    if (sc[FG_FLAG] != FG_RUN) return;
+    const double beta = sqrt(rank_sum(nr, in, 1));
+    if (*counter == 0) {
+        hist[0] = beta;
+        *counter = 1;
+        sc[FG_H0] = beta;
+    }
+    if (!isfinite(beta)) sc[FG_FLAG] = FG_BREAKDOWN;
+    else if (beta == 0.0 || *counter - 1 >= (int)sc[FG_MAXIT]) sc[FG_FLAG] = FG_STOPPED;
+    else {
+        sc[FG_G] = beta;
+        sc[FG_SCALE] = beta;
+    }
+}
+
 }  // namespace
 
 int dot_partial_count(int64_t n) { return (int)std::max<int64_t>(1, (n + kDotSpan - 1) / kDotSpan); }
@@ -2508,6 +2753,82 @@ void launch_bicg_xr(hipStream_t s, int64_t n, const double* sc, const double* ph
     const int g = dot_partial_count(n);
     hipLaunchKernelGGL(bicg_xr_kernel, dim3(g), dim3(kTPB), 0, s, (long long)n, sc, ph, sh, sv, t, rhat,
                        x, r, part_rr, part_rhr);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_fgmres_init(hipStream_t s, double* sc, double tol, int restart, int max_iter) {
+    hipLaunchKernelGGL(fgmres_init_kernel, dim3(1), dim3(64), 0, s, sc, tol, restart, max_iter);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_fgmres_keep(hipStream_t s, int64_t n, const double* sc, const double* z, double* Z, int64_t stride) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(fgmres_keep_kernel, dim3(grid_for(n)), dim3(kTPB), 0, s, (long long)n, sc, z, Z,
+                       (long long)stride);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_fgmres_dots(hipStream_t s, int64_t n, const double* sc, const double* w, const double* V,
+                        int64_t stride, double* part) {
+    const int g = dot_partial_count(n);
+    hipLaunchKernelGGL(fgmres_dots_kernel, dim3(g), dim3(kTPB), 0, s, (long long)n, sc, w, V, (long long)stride, part);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_fgmres_reduce(hipStream_t s, int g, const double* sc, const double* part, double* tmp, double* out) {
+    // the grid spans every possible column index: blocks past j return at once, so the launch
+    // (and a captured graph holding it) does not depend on restart
+    if (g <= kRedSpan) {
+        hipLaunchKernelGGL(fgmres_sum_partials_kernel, dim3(1, kFgMax), dim3(kTPB), 0, s, g, sc, part, (long long)g, out);
+    } else {
+        const int g1 = (g + kRedSpan - 1) / kRedSpan;
+        AMG_ASSERT(g1 <= kRedSpan);
+        hipLaunchKernelGGL(fgmres_sum_partials_kernel, dim3(g1, kFgMax), dim3(kTPB), 0, s, g, sc, part, (long long)g, tmp);
+        hipLaunchKernelGGL(fgmres_sum_partials_kernel, dim3(1, kFgMax), dim3(kTPB), 0, s, g1, sc, tmp, (long long)g1, out);
+    }
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_fgmres_c(hipStream_t s, int nr, const double* in, double* sc) {
+    static_assert(kFgMax <= 64, "one lane per column");
+    hipLaunchKernelGGL(fgmres_c_kernel, dim3(1), dim3(64), 0, s, nr, in, sc);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_fgmres_update(hipStream_t s, int64_t n, const double* sc, const double* V, int64_t stride,
+                          double* w, double* part) {
+    const int g = dot_partial_count(n);
+    hipLaunchKernelGGL(fgmres_update_kernel, dim3(g), dim3(kTPB), 0, s, (long long)n, sc, V, (long long)stride, w, part);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_fgmres_column(hipStream_t s, int nr, const double* in, double* sc, double* hist, int* counter) {
+    hipLaunchKernelGGL(fgmres_column_kernel, dim3(1), dim3(64), 0, s, nr, in, sc, hist, counter);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_fgmres_scale(hipStream_t s, int64_t n, const double* sc, const double* w, double* V,
+                         int64_t stride, double* vin) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(fgmres_scale_kernel, dim3(grid_for(n)), dim3(kTPB), 0, s, (long long)n, sc, w, V,
+                       (long long)stride, vin);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_fgmres_y(hipStream_t s, double* sc) {
+    hipLaunchKernelGGL(fgmres_y_kernel, dim3(1), dim3(64), 0, s, sc);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_fgmres_x(hipStream_t s, int64_t n, const double* sc, const double* Z, int64_t stride, double* x) {
+    if (n <= 0) return;
+    const int g = dot_partial_count(n);
+    hipLaunchKernelGGL(fgmres_x_kernel, dim3(g), dim3(kTPB), 0, s, (long long)n, sc, Z, (long long)stride, x);
+    HIP_CHECK(hipGetLastError());
+}
+
+void launch_fgmres_begin(hipStream_t s, int nr, const double* in, double* sc, double* hist, int* counter) {
+    hipLaunchKernelGGL(fgmres_begin_kernel, dim3(1), dim3(64), 0, s, nr, in, sc, hist, counter);
     HIP_CHECK(hipGetLastError());
 }
 

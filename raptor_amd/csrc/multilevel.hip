@@ -772,6 +772,106 @@ int32_t Solver::bicgstab(double* x, const double* b, int32_t max_iter, double to
     return count - 1;
 }
 
+// ---- AMG-preconditioned restarted FGMRES --------------------------------------
+// Right-preconditioned flexible GMRES, M = one V-cycle from zero, one-pass classical
+// Gram-Schmidt.  The column index j, the iteration count, the stop flag, g, cs, sn, the packed
+// H, c and y stay on the device (sc[FG_*]): the kernels read j there and take the basis base
+// pointers, so one launch sequence -- one captured graph, G_FGMRES_STEP -- serves every Arnoldi
+// step, and G_FGMRES_RESTART (back substitution, the x update over the J columns completed, r =
+// b - A x, beta, v_0) opens every cycle and closes the call.  The x update zeroes J, so the
+// closing launch after a mid-cycle stop applies exactly the completed columns once.  With tol ==
+// 0 nothing waits for the host before the history download.  The cycle is captured on fixed
+// addresses: v_j is also written to `vin`, and the cycle's output `zout` is copied to Z's slot j.
+int32_t Solver::fgmres(double* x, const double* b, int32_t restart, int32_t max_iter, double tol,
+                       double* hist_host, int32_t* status) {
+    AMG_CHECK(max_iter >= 0, "max_iter must be >= 0");
+    AMG_CHECK(restart >= 1 && restart <= kFgMax, "restart must be 1 .. AMG_FGMRES_MAX_RESTART");
+    RoctxRange range("ParMultilevel::fgmres");
+    DevMatrix& A = *A0;
+    const int64_t n = A.n_rows;
+    hipStream_t s = ctx->stream;
+    const int nr = ctx->host.nranks;
+    const int g = dot_partial_count(n);
+    const size_t ntmp = (size_t)kFgMax * ((size_t)g / 4096 + 1) + 64;
+    // both grow with restart only: a smaller restart runs in the same buffers and graphs (the
+    // basis pairs sit behind the three fixed vectors, restart is read from the device)
+    const size_t m = (size_t)std::max(restart, fgmres_room);
+    const size_t need = m * (size_t)g + ntmp + (size_t)kFgMax * (size_t)nr + kFgMax + FG_N;
+    // a fresh scratch is zeroed: after a stop the gated kernels leave partials unwritten and
+    // the reductions and allgathers still read them
+    if (grow_work(fgmres_vec, (2 * m + 3) * (size_t)n + 1, fgmres_scratch, need, {G_FGMRES_STEP, G_FGMRES_RESTART}))
+        HIP_CHECK(hipMemsetAsync(fgmres_scratch.p, 0, need * sizeof(double), s));
+    fgmres_room = (int32_t)m;
+    double* w = fgmres_vec.p;
+    double* vin = w + n;
+    double* zout = vin + n;
+    double* V = zout + n;
+    double* Z = V + n;
+    const int64_t stride = 2 * n;
+    double* part = fgmres_scratch.p;
+    double* tmp = part + m * (size_t)g;
+    double* gathered = tmp + ntmp;
+    double* local = gathered + (size_t)kFgMax * (size_t)nr;
+    double* sc = local + kFgMax;
+    begin_history(max_iter);
+    launch_fgmres_init(s, sc, tol, restart, max_iter);
+    // the rank sums of the dot product whose partials sit in part's first row
+    auto rank_sums = [&]() -> const double* {
+        launch_reduce_partials(s, g, part, tmp, local);
+        if (nr == 1) return local;
+        ctx->allgather(local, gathered, 1);
+        return gathered;
+    };
+    auto step = [&] {  // column j: z_j = M(v_j); w = A z_j; c; w -= sum c_i v_i; eta; rotations; v_{j+1}
+        launch_zero(s, n, zout);
+        cycle_rec(0, zout, vin, false, false);
+        par_apply(A, KM_SPMV, zout, nullptr, w, 0.0, nullptr);
+        launch_fgmres_keep(s, n, sc, zout, Z, stride);
+        launch_fgmres_dots(s, n, sc, w, V, stride, part);
+        launch_fgmres_reduce(s, g, sc, part, tmp, local);
+        if (nr > 1) ctx->allgather(local, gathered, (size_t)kFgMax);  // the j + 1 sums in one exchange
+        launch_fgmres_c(s, nr, nr > 1 ? gathered : local, sc);
+        launch_fgmres_update(s, n, sc, V, stride, w, part);
+        launch_fgmres_column(s, nr, rank_sums(), sc, hist.p, hist_counter.p);
+        launch_fgmres_scale(s, n, sc, w, V, stride, vin);
+    };
+    auto cycle_start = [&] {  // x += Z y over the columns completed; r = b - A x; beta; v_0
+        launch_fgmres_y(s, sc);
+        launch_fgmres_x(s, n, sc, Z, stride, x);
+        par_apply(A, KM_RESID, x, b, w, 0.0, nullptr);
+        launch_dot_partials(s, n, w, w, part);
+        launch_fgmres_begin(s, nr, rank_sums(), sc, hist.p, hist_counter.p);
+        launch_fgmres_scale(s, n, sc, w, V, stride, vin);
+    };
+    // one collective graph decision for both graphs (keyed by the caller's x, b)
+    agree_stale({G_FGMRES_STEP, G_FGMRES_RESTART}, x, b);
+    run(G_FGMRES_RESTART, x, b, cycle_start);
+    double flag = FG_RUN;
+    bool open = false;  // columns completed and not yet applied to x
+    for (int32_t it = 0; it < max_iter; ++it) {
+        run(G_FGMRES_STEP, x, b, step);
+        open = true;
+        if ((it + 1) % restart == 0 || it + 1 == max_iter) {
+            run(G_FGMRES_RESTART, x, b, cycle_start);
+            open = false;
+        }
+        if (tol > 0.0) {  // the device applied the stopping rules: the host only learns of it
+            flag = read_scalar(sc + FG_FLAG);
+            if (flag != FG_RUN) break;
+        }
+    }
+    if (open) run(G_FGMRES_RESTART, x, b, cycle_start);  // a stop inside a cycle: its columns
+    int count = 0;
+    HIP_CHECK(hipMemcpyAsync(&count, hist_counter.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&flag, sc + FG_FLAG, sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    ctx->graph_inflight = false;
+    AMG_ASSERT(count >= 1 && count <= max_iter + 1);
+    download_history(hist_host, (size_t)count);
+    *status = flag == FG_BREAKDOWN ? AMG_KRYLOV_BREAKDOWN : AMG_KRYLOV_OK;
+    return count - 1;
+}
+
 static int64_t spmv_bytes(const DevMatrix& M) {
     // a segment row map is one more index stream of the operator: 4 B per segment
     const int64_t map = M.row_seg > 0 ? 4 * (M.n_rows / M.row_seg) : 0;
